@@ -8,7 +8,7 @@ Workload: BASELINE.json configs[4] ("c5"), the configuration the north star
 reports at 1, 2, 4 and 8 GPUs: 64 B IPv4 TCP/UDP frames, a 65 536-rule table
 (16 IPs x 2048 listening ports + 32 768 connected 5-tuples, L2/MALL-resident),
 1 000 endpoints, 8M frames per drained rx ring.  Frames are resident in HBM
-when the timed region starts.  At N=1 the line also carries configs[1] ("c2":
+when the timed region starts.  With --full at N=1 the line also carries configs[1] ("c2":
 1M x 64 B frames, 16 rules) under the key "c2", measured the same way.
 
 One step = one poll round: every rx queue the rank owns is drained once (one
@@ -25,7 +25,14 @@ barrier and the max-over-ranks time).  --strong fixes the whole job's frames
 per step at 64M (c5) and splits the queues over the ranks; the default is
 weak scaling (fixed queues per rank).
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+Usage: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+A plain run sets up, warms up, times the K steps and prints the line with the
+value and ms_per_step.  --full adds everything else the line can carry (the
+per-launch probe and roofline, one result set per queue, the end-to-end loop
+with usn_finalize, the CPU baselines, c2 / c3 / c4 / c4tx under their own keys
+and the PCIe-inclusive rate).  --dump-outputs DIR writes what the last timed
+step left in its result sets as DIR/*.npy (Run.dump_outputs); the inputs are
+seeded, so two builds can be compared array for array.
 For N > 1 under torch.distributed.run (WORLD_SIZE set) each process is one
 rank and WORLD_SIZE must equal N.  Without a launcher, `--gpus N` starts N
 rank processes itself (before anything touches the GPU: launch_ranks) and
@@ -51,7 +58,10 @@ HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: HBM3E 8.0 TB/s
 LAUNCH_FRAMES = 1 << 24       # frames per launch the rings are grouped to (8 x 1M, or 2 x 8M)
 ROTATE_BYTES = 1 << 30        # distinct batch bytes per rank, > the 256 MiB Infinity Cache
 STRONG_FRAMES = 1 << 26       # --strong: 64M frames per step for the whole job
-PROBE_GROUP = 8               # calls per event pair of the per-call device-time probe
+DUMP_BYTES = 40 << 20         # --dump-outputs: bytes of the sampled arrays in all (with the
+                              # sample positions and the bin offsets < 64 MB of files)
+DUMP_SEED = 20240607          # of the sample positions
+PROBE_GROUP = 8              # calls per event pair of the per-call device-time probe
 METRIC = "Mpkts/s device-resident L4 classify @64B frames; HBM GB/s vs roofline"
 DEFAULT_FRAMES = {"c1": 1 << 20, "c1fixed": 1 << 20, "c2": 1 << 20, "c3": 1 << 18, "c4": 1 << 20,
                   "c5": 1 << 23}
@@ -79,6 +89,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the line can carry: the per-launch "
+                         "probe and roofline, one result set per queue, the end-to-end loop, the CPU "
+                         "baselines, the other configs' keys and the PCIe-inclusive rate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (decisions, per-endpoint lists) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--config", default="c5")
     ap.add_argument("--frames", type=int, default=0, help="frames per batch (default: config's)")
     ap.add_argument("--queues", type=int, default=0,
@@ -381,6 +398,31 @@ class Run:
                 cls = [x + y for x, y in zip(cls, info.class_count)]
         return host_frames, flags, cls
 
+    def dump_outputs(self, path, step, prefix=""):
+        """--dump-outputs: what poll round `step` left in its result sets, as a
+        caller of usn_classify_multi receives them once the streams are idle:
+        per queue j the decision words, the per-endpoint lists' frame indices
+        and their bin offsets, as <path>/<prefix>q<j>_{decisions,index,bin_off}.npy
+        (float64: exact for the 32-bit words).  Arrays longer than the dump's
+        budget are sampled at fixed, seeded positions (sample_positions.npy,
+        the same for every array and every run)."""
+        os.makedirs(path, exist_ok=True)
+        for x in self.streams:
+            self.ctx.sync(x)
+        cap = DUMP_BYTES // 8 // (2 * self.Q)
+        pos = None
+        if self.n > cap:
+            pos = np.sort(np.random.default_rng(DUMP_SEED).choice(self.n, cap, replace=False))
+            np.save(os.path.join(path, prefix + "sample_positions.npy"), pos.astype(np.float64))
+        rnd = step % self.RR
+        for j in range(self.Q):
+            r = self.results[rnd * self.Q + j]
+            for name, a in (("decisions", r.decisions()), ("index", r.index())):
+                np.save(os.path.join(path, "%sq%d_%s.npy" % (prefix, j, name)),
+                        (a if pos is None else a[pos]).astype(np.float64))
+            np.save(os.path.join(path, "%sq%d_bin_off.npy" % (prefix, j)),
+                    r.bin_off().astype(np.float64))
+
     def free(self):
         for b in self.batches:
             b.free()
@@ -415,12 +457,28 @@ def measure(run, args, dist, world):
     # (profiles/r02aq; 200 rounds cost ~0.1 s).
     for i in range(args.ramp):
         run.step(args.warmup + i)
-    kern_ms, probe_frames = run.launch_probe(args.launch_probe) if args.launch_probe else (None, 0)
+    probe = args.launch_probe if args.full else 0    # a plain run: the ramp rounds only
+    kern_ms, probe_frames = run.launch_probe(probe) if probe else (None, 0)
     for i in range(args.ramp):      # again: the one-stream probe lets the rate drop
         run.step(args.warmup + args.ramp + i)
     wall, ev_ms = run.timed(args.steps, dist)
     elapsed = shard.max_over_ranks(wall, dist)
     enqueue_s = run.enqueue_s
+    if args.dump_outputs:           # before any later loop writes the result sets again
+        run.dump_outputs(args.dump_outputs, args.steps - 1,
+                         "rank%d_" % dist.get_rank() if dist else "")
+    head = {
+        "value": round(world * args.steps * run.frames_per_step() / elapsed / 1e6, 2),
+        "value_basis": "K poll rounds, round i into result set i mod %d of each queue (the daemon's "
+                       "double-buffered results), no usn_finalize in the loop" % run.RR,
+        "ms_per_step": round(elapsed * 1e3 / args.steps, 5),
+        "event_ms_per_step": round(ev_ms / args.steps, 5),
+        # the host's own time to enqueue a step's calls (close to ms_per_step: host-bound)
+        "enqueue_ms_per_step": round(enqueue_s * 1e3 / args.steps, 5),
+        "frames_per_step_per_gpu": run.frames_per_step(),
+    }
+    if not args.full:
+        return head
     # the same K rounds with one result set per queue rewritten every round
     # (rounds 0 .. R - 1 only; round 5's value basis), reported beside the value
     wall1, _ = run.timed(args.steps, dist, single=True)
@@ -466,9 +524,7 @@ def measure(run, args, dist, world):
         except (OSError, ValueError):
             pass
     return {
-        "value": round(frames / elapsed / 1e6, 2),
-        "value_basis": "K poll rounds, round i into result set i mod %d of each queue (the daemon's "
-                       "double-buffered results), no usn_finalize in the loop" % run.RR,
+        **head,
         "value_single_result_set": round(frames / elapsed1 / 1e6, 2),
         "end_to_end_mpps": round(frames / e2e_elapsed / 1e6, 2),
         "end_to_end": {
@@ -482,11 +538,6 @@ def measure(run, args, dist, world):
             "finalize_host_us_per_ring": round(fin_host_us, 2),
             "rings_per_step": run.Q,
         },
-        "ms_per_step": round(elapsed * 1e3 / args.steps, 5),
-        "event_ms_per_step": round(ev_ms / args.steps, 5),
-        # the host's own time to enqueue a step's calls (close to ms_per_step: host-bound)
-        "enqueue_ms_per_step": round(run.enqueue_s * 1e3 / args.steps, 5),
-        "frames_per_step_per_gpu": run.frames_per_step(),
         "host_stage_frames": int(host_frames),
         "summary_flags": int(flags),
         "class_count_last_rotation": [int(x) for x in cls],
@@ -867,9 +918,6 @@ def main(argv=None):
         "value": res["value"],
         "unit": "Mpkts/s",
         "value_basis": res["value_basis"],
-        "value_single_result_set": res["value_single_result_set"],
-        "end_to_end_mpps": res["end_to_end_mpps"],
-        "end_to_end": res["end_to_end"],
         "n_gpus": len(joined),
         "steps": args.steps,
         "warmup": args.warmup,
@@ -894,27 +942,30 @@ def main(argv=None):
             "lists_async": bool(args.lists_async),
             "untimed_ramp_steps": 2 * args.ramp,
             "frames_per_step_per_gpu": res["frames_per_step_per_gpu"],
-            "host_stage_frames": res["host_stage_frames"],
-            "summary_flags": res["summary_flags"],
-            "class_count_last_rotation": res["class_count_last_rotation"],
         },
-        "roofline": res["roofline"],
-        "cpu_baseline": None,
+        "full": args.full,
     }
+    if args.full:
+        for k in ("value_single_result_set", "end_to_end_mpps", "end_to_end", "roofline"):
+            out[k] = res[k]
+        for k in ("host_stage_frames", "summary_flags", "class_count_last_rotation"):
+            out["config"][k] = res[k]
+        out["cpu_baseline"] = None
     cfg0 = run.cfg0
     run.free()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    full1 = args.full and world == 1      # what only a --full run at N=1 adds
+    if rank == 0 and full1 and not args.no_cpu_baseline:
         # pinned like configs[0] (/root/reference/eval/Makefile:22
         # runs the matcher under `taskset -c 6`): one spawned process on one
         # CPU, and one pinned process per CPU of the job's share
         out["cpu_baseline"] = cpu_pinned_1core(args.config, args.cpu_seconds, nshard=1 << 20)
         out["cpu_baseline_ncores"] = cpu_baseline_ncores(args.config, args.cpu_seconds, pin=True)
     del cfg0
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_extra:
+    if rank == 0 and full1 and not args.no_cpu_baseline and not args.no_extra:
         # configs[0], the CPU-only config, in both traffic variants
         for name in ("c1", "c1fixed"):
             out[name] = measure_c1(name, min(args.cpu_seconds, 3.0))
-    if world == 1 and not args.no_extra:
+    if full1 and not args.no_extra:
         # the other BASELINE configs, each measured the same way, under its own
         # key: configs[1] (c2), configs[2] (c3: IMIX in 2048-byte slots) and
         # configs[3] in both directions (c4 rx, c4tx: the ADD_MACS learned-MAC
@@ -931,13 +982,14 @@ def main(argv=None):
                          args.streams, False, result_rounds=args.result_rounds)
                 xa = argparse.Namespace(**vars(args))
                 xa.steps = max(args.steps, EXTRA_MIN_STEPS.get(name, 0))
+                xa.dump_outputs = None           # the dump is the headline config's
                 x = measure(rx, xa, None, 1)
                 x["workload"] = workload(rx, False)
                 if not args.no_cpu_baseline:
                     x["cpu_baseline"] = cpu_pinned_1core(name, min(args.cpu_seconds, 3.0))
                 rx.free()
             out[name] = x
-    if world == 1 and not args.no_extra and args.host_inclusive:
+    if full1 and not args.no_extra and args.host_inclusive:
         # the PCIe-inclusive rate of c5 and c2 (frames and results in pinned
         # host memory), beside the device-resident value
         out["host_inclusive"] = {}

@@ -58,3 +58,12 @@ def test_bench_defaults_match_the_driver_contract():
     assert a.tx_rings == 8
     assert set(a.host_inclusive.split(",")) == {"c5", "c2"}
     assert bench.parse_args(["--tx-launches", "13"]).tx_launches == 13
+
+
+def test_plain_run_is_the_default():
+    """--full (everything beside the headline) and --dump-outputs are off
+    unless asked for."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"

@@ -100,7 +100,7 @@ def test_bench_self_launch_two_ranks():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                          "--config", "c2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                          "--config", "c2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
                           "--no-extra", "--launch-probe", "4", "--ramp", "2"],
                          env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -32,10 +32,10 @@ for s in "$@"; do
     tests) step pytest_gpu 1100 python -u -m pytest ${TESTS:-tests} -m gpu -q -x -rf --timeout 300 --timeout-method thread ${TEST_K:+-k "$TEST_K"} ;;
     testsall) step pytest_gpu 1100 python -u -m pytest ${TESTS:-tests} -m gpu -q -rf --timeout 300 --timeout-method thread ${TEST_K:+-k "$TEST_K"} ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python bench.py ${BENCH_ARGS:---steps 20 --warmup 5} ;;
-    bench_n2) TAILN=2 step bench_n2 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 10 --warmup 2 --no-cpu-baseline --no-extra ;;
+    bench) step bench 600 python bench.py --full ${BENCH_ARGS:---steps 20 --warmup 5} ;;
+    bench_n2) TAILN=2 step bench_n2 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 10 --warmup 2 --full --no-cpu-baseline --no-extra ;;
     rocprof) rm -rf $O/prof
-      step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --ramp 40 ${ROCPROF_ARGS:-}
+      step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --ramp 40 ${ROCPROF_ARGS:-}
       step trace_summary 60 python3 tools/trace_summary.py $O/prof/run_kernel_trace.csv ;;
     pmc)  # FETCH_SIZE / WRITE_SIZE passes per config of PMC_CFGS through bench.py's launch shape
       for c in ${PMC_CFGS:-c5 c2}; do
