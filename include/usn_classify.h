@@ -387,6 +387,78 @@ typedef int (*usn_frame_reader)(void *user, uint16_t src_endpoint, uint64_t inde
                                 uint32_t cap);
 int usn_set_frame_reader(usn_ctx *ctx, usn_frame_reader fn, void *user);
 
+/* ---- delivery: each endpoint's output ring, packed on the device -----------
+ * The step after the decision (the reference writes a frame into its target's
+ * ring, endpoint.rs:61-74, and copies ARP / EAPOL frames to every other
+ * endpoint, mirror_to_all, :340-363): for a classified batch of source s whose
+ * lists are final, receiver e gets, in ascending frame index, every frame that
+ * is class EP with ep == e, class NIC when e == for_nic(s), or class FLOOD
+ * when e != s; DROP frames go nowhere.  Receivers are the endpoints registered
+ * in the context when usn_deliver is called: an id with a non-empty bin that
+ * is no longer registered receives nothing, and a registered id at or above
+ * the batch's summary.n_ep can only receive FLOOD.  The result is one
+ * contiguous, frame-ordered region of whole frames per endpoint (one D2H copy,
+ * a sendmmsg vector or a ring).
+ *
+ * Sizing: need = sum of the receivers' own bins + n_nic + n_flood x
+ * (receivers - 1) slots ((receivers) when the source is not registered).
+ * When need > cap the plan sets USN_DV_OVERFLOW and no slot is written;
+ * ep_off and hdr->need are still valid, so the caller sizes a retry or falls
+ * back to the lists.  A frame longer than `slot` is copied truncated to
+ * `slot`; lens[k] holds its true length and USN_DV_LONG is set.
+ *
+ * In output slot k, bytes [0, len) equal the frame and bytes [len,
+ * ceil16(len)) are zero (ceil16: rounded up to a multiple of 16); the rest of
+ * the slot is not written.  Every delivered frame must be readable over its
+ * first ceil16(len) bytes, not just over usn_batch.window.
+ *
+ * For a batch that needs the host stage, deliver after usn_finalize: the
+ * lists are final only then (see usn_result). */
+#define USN_HAS_DELIVER 1
+#define USN_DELIVER_TILE 512   /* output slots per pack tile (one workgroup pass) */
+#define USN_DV_OVERFLOW 1u     /* need > cap: nothing was packed */
+#define USN_DV_LONG 2u         /* a delivered frame's len > slot (copied truncated) */
+typedef struct {
+  uint32_t need;           /* slots this batch needs (sum over receivers) */
+  uint32_t cap;            /* slots the delivery holds */
+  uint32_t flags;          /* USN_DV_* */
+  uint32_t n_recv;         /* receivers with at least one frame */
+} usn_delivery_hdr;
+typedef struct {
+  uint8_t *frames;         /* cap * slot bytes; output slot k at frames + k*slot */
+  uint16_t *lens;          /* cap: length of the frame in slot k */
+  uint32_t *src;           /* cap: batch frame index the slot was copied from */
+  uint32_t *ep_off;        /* USN_MAX_ENDPOINTS + 1: ring of endpoint e = slots [ep_off[e], ep_off[e+1]) */
+  usn_delivery_hdr *hdr;   /* followed by the plan's scratch (the pack grid's tile prefix) */
+  uint64_t cap;
+  uint32_t slot;           /* bytes per output slot: a multiple of 16 */
+  uint32_t _r;
+} usn_delivery;
+/* Bytes of a delivery of cap_slots slots of `slot` bytes (0 for a slot that is
+ * 0 or no multiple of 16, or cap_slots 0 or >= 2^32); usn_delivery_bind carves
+ * device (or, for layout checks, host) memory of that size: USN_EINVAL for
+ * such a slot or cap, USN_ERANGE when `bytes` is too small. */
+size_t usn_delivery_bytes(uint64_t cap_slots, uint32_t slot);
+int usn_delivery_bind(void *dev_mem, size_t bytes, uint64_t cap_slots, uint32_t slot, usn_delivery *out);
+/* Packs the rings of batch `b` classified into `r` (on r's replica).
+ * Asynchronous on `hip_stream`, ordered after the result's lists as
+ * usn_lists_wait orders them; reads bin_off, index, summary.n_ep and lens on
+ * the device; no host synchronisation and no copy in the steady state.  The
+ * receiver table (registered ids and their for_nic) is a small device table
+ * per replica, uploaded synchronously before the launch only after the
+ * endpoint set changed (the device is drained first, so an earlier delivery
+ * still reads the table it was launched with).
+ * USN_EINVAL: a null pointer, n >= 2^32 - 1, a result no batch was classified
+ * into, slot 0 / no multiple of 16 / smaller than a strided batch's stride;
+ * USN_EBUSY: r belongs to a tx batch not yet finalized; USN_ENODEV: a
+ * USN_HOST_ONLY context. */
+int usn_deliver(usn_ctx *ctx, const usn_batch *b, const usn_result *r, usn_delivery *d,
+                void *hip_stream);
+/* Synchronises `hip_stream` and copies the header to the host: USN_ERANGE
+ * when either flag is set (host_out is filled all the same). */
+int usn_deliver_info(usn_ctx *ctx, const usn_delivery *d, void *hip_stream,
+                     usn_delivery_hdr *host_out);
+
 /* Forget the carried decision cache of one endpoint (last_pkt = None). */
 int usn_cache_clear(usn_ctx *ctx, uint16_t endpoint);
 

@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Device time of usn_deliver on classified calls of a config, next to a
+device-to-device copy of the same n x slot bytes (the yardstick: the gather
+moves the same frame bytes plus 6 B/frame of index and lens read and 6 B/frame
+of src and lens written) and to the classify + lists call that precedes it.
+
+A call is `--multi` rings of `--frames` frames classified by one
+usn_classify_multi (c5: 2 x 8M, c2: 8 x 1M), then one usn_deliver per ring.
+Inputs, results and deliveries rotate over `--rounds` distinct device sets
+(> the 256 MiB Infinity Cache in all); deliver and copy alternate in blocks so
+both see the same neighbours.  Times are device events on the one stream.
+
+usage: python tools/deliver_bench.py [--config c5] [--frames N] [--multi 2] [--rounds 2]
+                                     [--launches 120] [--slot 64] [--json out.json]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from usnetd_amd import lib, traffic  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="c5")
+    ap.add_argument("--frames", type=int, default=1 << 23)
+    ap.add_argument("--multi", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--launches", type=int, default=120)
+    ap.add_argument("--slot", type=int, default=64)
+    ap.add_argument("--json", default="")
+    a = ap.parse_args()
+    n, Q, R = a.frames, a.multi, a.rounds
+    cfgs = [traffic.config(a.config, n=n, seed=17 * k + 2) for k in range(Q)]
+    ctx = lib.Ctx(0)
+    traffic.install_ctx(ctx, cfgs[0])
+    nics = [cfgs[0].src] + list(traffic.extra_nics(cfgs[0], Q - 1, ctx))
+    n_ep = max(nics) + 1
+    s = ctx.stream()
+    # R device sets of the call's rings, results and deliveries
+    bs = [[lib.DeviceBatch(ctx, c.frames, c.lens, nics[k], stride=c.stride) for k, c in enumerate(cfgs)]
+          for _ in range(R)]
+    rs = [[lib.DeviceResult(ctx, n, max_endpoints=n_ep) for _ in range(Q)] for _ in range(R)]
+    dvs = [[lib.DeviceDelivery(ctx, n, a.slot) for _ in range(Q)] for _ in range(R)]
+    copy_src = [[b.buf.ptr for b in row] for row in bs]
+    copy_dst = [[d.desc.frames for d in row] for row in dvs]
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpyDtoDAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+
+    def classify(r):
+        ctx.classify_multi(bs[r], rs[r], s)
+
+    def deliver(r):
+        for k in range(Q):
+            ctx.deliver(bs[r][k], rs[r][k], dvs[r][k], s)
+
+    def copy(r):
+        for k in range(Q):
+            assert hip.hipMemcpyDtoDAsync(copy_dst[r][k], copy_src[r][k], n * a.slot, s) == 0
+
+    def timed(fn, count, after=None):
+        evs = [(ctx.event(), ctx.event()) for _ in range(count)]
+        for i, (x, y) in enumerate(evs):
+            ctx.record(x, s)
+            fn(i % R)
+            ctx.record(y, s)
+            if after:
+                after(i % R)
+        ctx.sync(s)
+        return [ctx.elapsed_ms(x, y) * 1e3 for x, y in evs]
+
+    def finalize(r):
+        for k in range(Q):
+            ctx.finalize(bs[r][k], rs[r][k], s)
+
+    for r in list(range(R)) * 2:   # warm-up: every set classified, delivered and copied
+        classify(r)
+        finalize(r)
+        deliver(r)
+        copy(r)
+    ctx.sync(s)
+    cls_us = timed(classify, max(20, 2 * R), after=finalize)
+    # what the deliveries hold: the header, and the slots against the lists
+    need = 0
+    for r in range(R):
+        deliver(r)
+        for k in range(Q):
+            h = dvs[r][k].info(s)
+            off = rs[r][k].bin_off()
+            assert h.need == int(off[int(rs[r][k].summary()["n_ep"])]), "need differs from the endpoint bins"
+            need += h.need if r == 0 else 0
+    src0, len0, _ = dvs[0][0].ring(2)
+    assert np.array_equal(src0, rs[0][0].lists().get(2, np.zeros(0, np.uint32))) and (len0 == 64).all()
+    dl_us, cp_us = [], []
+    block = 30
+    while len(dl_us) < a.launches:
+        dl_us += timed(deliver, block)
+        cp_us += timed(copy, block)
+    frames = n * Q
+    dl, cp, cl = (statistics.median(x) for x in (dl_us, cp_us, cls_us))
+    moved = need * (2 * a.slot + 12)          # frame read + write, index + lens read, src + lens written
+    out = dict(config=a.config, frames_per_call=frames, rings=Q, slot=a.slot, delivered_slots=need,
+               deliver_us=round(dl, 1), deliver_min_us=round(min(dl_us), 1),
+               deliver_p90_us=round(float(np.percentile(dl_us, 90)), 1), deliver_launches=len(dl_us),
+               deliver_bytes_per_frame=round(moved / frames, 1), deliver_gbps=round(moved / dl / 1e3, 1),
+               d2d_copy_us=round(cp, 1), d2d_copy_min_us=round(min(cp_us), 1),
+               d2d_copy_gbps=round(2 * frames * a.slot / cp / 1e3, 1),
+               deliver_over_copy=round(dl / cp, 2), classify_lists_us=round(cl, 1),
+               deliver_share_of_call=round(dl / (dl + cl), 3))
+    print(json.dumps(out), flush=True)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

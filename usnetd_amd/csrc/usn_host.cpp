@@ -493,6 +493,10 @@ struct Replica {
   // (hipHostGetDevicePointer once, not per call)
   uint32_t *d_rxstate = nullptr, *d_txstate = nullptr;
   uint32_t rx_ev_next = 0;
+  /* usn_deliver's receiver table (DeliverArgs::eptab) at the endpoint-set
+   * version it was uploaded for (0 = none) */
+  uint16_t *d_eptab = nullptr;
+  uint64_t eptab_version = 0;
 };
 
 /* The completion events of rx and tx launches (usn_finalize waits for its
@@ -531,6 +535,7 @@ struct usn_ctx {
   std::mutex mu;
   std::vector<Ep> eps = std::vector<Ep>(USN_MAX_ENDPOINTS);
   uint32_t n_ep = 0;   // max id + 1
+  uint64_t ep_version = 1;   // bumped by every endpoint add / remove (Replica::eptab_version)
   RuleMap rules;
   std::vector<uint64_t> bridge;
   std::unordered_map<FragKey, FragVal, FragHash> frags;
@@ -1938,7 +1943,7 @@ void usn_ctx_destroy(usn_ctx *c) {
     for (void *p : {(void *)R.d_table, R.d_patch, (void *)R.d_bridge, (void *)R.d_bridge_set,
                     (void *)R.aux, (void *)R.macset, (void *)R.ruleset, (void *)R.txs[0].learned,
                     (void *)R.txs[0].counters, (void *)R.txs[1].learned, (void *)R.txs[1].counters,
-                    (void *)R.listen})
+                    (void *)R.listen, (void *)R.d_eptab})
       if (p) (void)hipFree(p);
   }
   for (auto &kv : c->lists_ev)
@@ -1986,6 +1991,7 @@ int usn_endpoint_add(usn_ctx *c, uint16_t id, int kind, int32_t for_nic) {
   e.for_nic = for_nic;
   e.listen_ver = ++c->listen_gen;
   c->n_ep = std::max<uint32_t>(c->n_ep, (uint32_t)id + 1);
+  ++c->ep_version;
   c->chains[id] = Chain();
   return USN_OK;
 }
@@ -2005,6 +2011,7 @@ int usn_endpoint_remove(usn_ctx *c, uint16_t id) {
   }
   c->eps[id] = Ep();
   c->chains[id] = Chain();
+  ++c->ep_version;
   return USN_OK;
 }
 
@@ -3747,6 +3754,115 @@ int usn_lists_wait(usn_ctx *c, const usn_result *r, void *stream) {
   HIPCHK(hipSetDevice(it->second.device));
   HIPCHK(hipStreamWaitEvent((hipStream_t)stream, it->second.ev, 0));
   return USN_OK;
+}
+
+/* ---- delivery: the per-endpoint output rings (usn_deliver.hip) -------------- */
+struct DeliveryLayout {
+  size_t frames, lens, src, ep_off, hdr, total;
+};
+static bool delivery_layout(uint64_t cap, uint32_t slot, DeliveryLayout &L) {
+  if (slot == 0 || slot % 16 != 0 || cap == 0 || cap > 0xFFFFFFFFull) return false;
+  size_t off = 0;
+  L.frames = off; off = align256(off + (size_t)cap * slot);
+  L.lens = off; off = align256(off + (size_t)cap * 2);
+  L.src = off; off = align256(off + (size_t)cap * 4);
+  L.ep_off = off; off = align256(off + (size_t)USN_DT_IDS * 4);
+  L.hdr = off; off = align256(off + usn::DELIVER_SCRATCH_OFF + usn::DELIVER_SCRATCH_BYTES);
+  L.total = off;
+  return true;
+}
+
+size_t usn_delivery_bytes(uint64_t cap_slots, uint32_t slot) {
+  DeliveryLayout L;
+  return delivery_layout(cap_slots, slot, L) ? L.total : 0;
+}
+
+int usn_delivery_bind(void *mem, size_t bytes, uint64_t cap_slots, uint32_t slot, usn_delivery *out) {
+  DeliveryLayout L;
+  if (!mem || !out || ((uintptr_t)mem & 15) != 0 || !delivery_layout(cap_slots, slot, L)) return USN_EINVAL;
+  if (bytes < L.total) return USN_ERANGE;
+  uint8_t *b = static_cast<uint8_t *>(mem);
+  out->frames = b + L.frames;
+  out->lens = reinterpret_cast<uint16_t *>(b + L.lens);
+  out->src = reinterpret_cast<uint32_t *>(b + L.src);
+  out->ep_off = reinterpret_cast<uint32_t *>(b + L.ep_off);
+  out->hdr = reinterpret_cast<usn_delivery_hdr *>(b + L.hdr);
+  out->cap = cap_slots;
+  out->slot = slot;
+  out->_r = 0;
+  return USN_OK;
+}
+
+/* the receiver table of replica R at today's endpoint set.  Rare (the
+ * endpoint set changed): the device drains first, so a delivery launched
+ * before still reads the table it was launched with; the copy is synchronous */
+static int upload_eptab(usn_ctx *c, Replica &R) {
+  if (R.d_eptab && R.eptab_version == c->ep_version) return USN_OK;
+  HIPCHK(hipSetDevice(R.device));
+  if (!R.d_eptab) HIPCHK(hipMalloc((void **)&R.d_eptab, (size_t)USN_DT_IDS * 2));
+  std::vector<uint16_t> tab(USN_DT_IDS, (uint16_t)USN_DT_NONE);
+  for (uint32_t e = 0; e < USN_MAX_ENDPOINTS; ++e)
+    if (c->eps[e].used) tab[e] = c->eps[e].for_nic < 0 ? (uint16_t)USN_DT_NONIC : (uint16_t)c->eps[e].for_nic;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(R.d_eptab, tab.data(), tab.size() * 2, hipMemcpyHostToDevice));
+  R.eptab_version = c->ep_version;
+  return USN_OK;
+}
+
+int usn_deliver(usn_ctx *c, const usn_batch *b, const usn_result *r, usn_delivery *d, void *stream) {
+  if (!c || !b || !r || !d) return USN_EINVAL;
+  if (!b->frames || !b->lens || !r->index || !r->bin_off || !r->summary || !r->decisions ||
+      !d->frames || !d->lens || !d->src || !d->ep_off || !d->hdr)
+    return USN_EINVAL;
+  if (b->n == 0 || b->n >= 0xFFFFFFFFull || r->n < b->n) return USN_EINVAL;
+  if ((b->stride == 0) == (b->offsets == nullptr)) return USN_EINVAL;
+  if (d->slot == 0 || d->slot % 16 != 0 || (b->stride && d->slot < b->stride)) return USN_EINVAL;
+  if (d->cap == 0 || d->cap > 0xFFFFFFFFull || b->src_endpoint >= USN_MAX_ENDPOINTS) return USN_EINVAL;
+  if ((((uintptr_t)b->frames | (uintptr_t)d->frames) & 15) != 0 || (b->stride & 15) != 0) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  std::lock_guard<std::mutex> g(c->mu);
+  for (const usn_ctx::Tx &t : c->txq)
+    if (t.decisions == r->decisions) return USN_EBUSY;   // lists not final before its usn_finalize
+  const auto br = c->batch_rep.find(r->decisions);
+  if (br == c->batch_rep.end()) return USN_EINVAL;       // nothing was classified into r
+  Replica &R = c->reps[br->second.rep];
+  { int s = upload_eptab(c, R); if (s) return s; }
+  HIPCHK(hipSetDevice(R.device));
+  const auto le = c->lists_ev.find(r->decisions);        // lists built on the side stream
+  if (le != c->lists_ev.end() && le->second.ev)
+    HIPCHK(hipStreamWaitEvent((hipStream_t)stream, le->second.ev, 0));
+  usn::DeliverArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.frames = b->frames;
+  a.stride = b->stride;
+  a.offsets = b->offsets;
+  a.lens = b->lens;
+  a.n = (uint32_t)b->n;
+  a.src = b->src_endpoint;
+  a.index = r->index;
+  a.bin_off = r->bin_off;
+  a.summary = r->summary;
+  a.eptab = R.d_eptab;
+  a.out_frames = d->frames;
+  a.out_lens = d->lens;
+  a.out_src = d->src;
+  a.ep_off = d->ep_off;
+  a.hdr = d->hdr;
+  a.tile_pfx = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(d->hdr) + usn::DELIVER_SCRATCH_OFF);
+  a.cap = (uint32_t)d->cap;
+  a.slot = d->slot;
+  // a grid the device holds at once (8 workgroups of 256 threads per CU), whatever the batch
+  HIPCHK(usn::launch_deliver(a, (uint32_t)std::max(R.n_cu, 1) * 8u, (hipStream_t)stream));
+  if (c->sel < c->reps.size() && c->reps[c->sel].device != R.device) HIPCHK(hipSetDevice(c->device));
+  return USN_OK;
+}
+
+int usn_deliver_info(usn_ctx *c, const usn_delivery *d, void *stream, usn_delivery_hdr *out) {
+  if (!c || !d || !d->hdr || !out) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  HIPCHK(hipMemcpy(out, d->hdr, sizeof *out, hipMemcpyDeviceToHost));
+  return out->flags & (USN_DV_OVERFLOW | USN_DV_LONG) ? USN_ERANGE : USN_OK;
 }
 
 /* ---- device plumbing ------------------------------------------------------- */

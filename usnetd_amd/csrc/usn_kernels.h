@@ -236,6 +236,47 @@ void scatter_carve(void *scratch, uint64_t cap, uint64_t n, uint32_t nbins, uint
 void scatter_tail(void *scratch, uint64_t cap, uint32_t nbins, void **p, size_t *bytes);
 uint32_t *scatter_diag(void *scratch, uint64_t cap, uint32_t nbins);
 
+/* ---- delivery (usn_deliver.hip): the per-endpoint output rings ------------
+ * Two launches on the caller's stream:
+ *   deliver_plan_kernel  one workgroup: per endpoint id the slots it receives
+ *                        (its own bin, the NIC bin for the source's NIC, the
+ *                        FLOOD bin for every registered id but the source),
+ *                        their exclusive scan (ep_off), the header, and the
+ *                        prefix of output tiles per receiver (tile_pfx)
+ *   deliver_pack_kernel  a grid sized to the device; each workgroup loops
+ *                        over output tiles of USN_DELIVER_TILE slots: finds
+ *                        the tile's receiver and its cut into the receiver's
+ *                        up to three sorted lists, merges the runs after the
+ *                        cuts in LDS, writes src[] / lens[] and gathers the
+ *                        frames with 128-bit loads and stores */
+#define USN_DT_NONE 0xFFFFu     /* eptab[e]: id e is not registered */
+#define USN_DT_NONIC 0xFFFEu    /* ... registered, a NIC itself (no for_nic) */
+#define USN_DT_IDS (USN_MAX_ENDPOINTS + 1u)   /* 4096: ids scanned (the last is never registered) */
+struct DeliverArgs {
+  const uint8_t *frames;
+  uint64_t stride;
+  const uint64_t *offsets;
+  const uint16_t *lens;
+  uint32_t n;               /* frames in the batch (< 2^32 - 1) */
+  uint32_t src;             /* the batch's source endpoint */
+  const uint32_t *index;
+  const uint32_t *bin_off;
+  const usn_summary *summary;
+  const uint16_t *eptab;    /* [USN_DT_IDS]: for_nic of a registered id, USN_DT_NONIC, USN_DT_NONE */
+  uint8_t *out_frames;
+  uint16_t *out_lens;
+  uint32_t *out_src;
+  uint32_t *ep_off;         /* [USN_DT_IDS] */
+  usn_delivery_hdr *hdr;
+  uint32_t *tile_pfx;       /* [USN_DT_IDS]: output tiles of the ids below; the last entry is
+                               the tile total (0 on overflow) */
+  uint32_t cap, slot;
+};
+/* bytes from usn_delivery.hdr to the plan's scratch (tile_pfx) */
+constexpr size_t DELIVER_SCRATCH_OFF = 256;
+constexpr size_t DELIVER_SCRATCH_BYTES = (size_t)USN_DT_IDS * 4;
+hipError_t launch_deliver(const DeliverArgs &a, uint32_t pack_grid, hipStream_t stream);
+
 }  // namespace usn
 
 /* the same kernels at 512 threads per tile (a second compilation of

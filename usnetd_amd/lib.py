@@ -23,6 +23,8 @@ USN_WINDOW = 64
 USN_WINDOW_MAX = 80
 USN_MAX_ENDPOINTS = 4095
 USN_MAX_BINS = USN_MAX_ENDPOINTS + 3
+USN_DELIVER_TILE = 512   # output slots per pack tile of usn_deliver (usn_classify.h)
+DV_OVERFLOW, DV_LONG = 1, 2
 R_WINDOW = 7
 PARITY_MASK = 0x00FFFFFF
 EP_NIC, EP_HOST, EP_PIPE, EP_UDS = 0, 1, 2, 3
@@ -34,6 +36,8 @@ STATUS = {0: "ok", -22: "EINVAL", -12: "ENOMEM", -17: "EEXIST", -2: "ENOENT", -1
           -5: "EHIP", -19: "ENODEV", -34: "ERANGE", -16: "EBUSY", -74: "ELIST"}
 USN_EBUSY = -16
 USN_EINVAL = -22
+USN_ERANGE = -34
+USN_ENODEV = -19
 USN_ELIST = -74
 
 
@@ -68,6 +72,17 @@ class Result(C.Structure):
 class FinalizeInfo(C.Structure):
     _fields_ = [("n_host", C.c_uint32), ("n_patched", C.c_uint32), ("n_learned", C.c_uint32),
                 ("flags", C.c_uint32), ("class_count", C.c_uint32 * 4)]
+
+
+class DeliveryHdr(C.Structure):
+    _fields_ = [("need", C.c_uint32), ("cap", C.c_uint32), ("flags", C.c_uint32),
+                ("n_recv", C.c_uint32)]
+
+
+class Delivery(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("lens", C.c_void_p), ("src", C.c_void_p),
+                ("ep_off", C.c_void_p), ("hdr", C.c_void_p), ("cap", C.c_uint64),
+                ("slot", C.c_uint32), ("_r", C.c_uint32)]
 
 
 TILE_HDR_DTYPE = np.dtype([("n_frames", "<u2"), ("_r0", "<u2"), ("n_host", "<u2"),
@@ -132,10 +147,15 @@ def load(path: str | None = None):
         "usn_ctx_replicas": ([P], I), "usn_replica_select": ([P, U32], I),
         "usn_replica_device": ([P, U32], I),
         "usn_set_lists_async": ([P, I], I), "usn_lists_wait": ([P, C.POINTER(Result), P], I),
+        "usn_delivery_bytes": ([U64, U32], SZ),
+        "usn_delivery_bind": ([P, SZ, U64, U32, C.POINTER(Delivery)], I),
+        "usn_deliver": ([P, C.POINTER(Batch), C.POINTER(Result), C.POINTER(Delivery), P], I),
+        "usn_deliver_info": ([P, C.POINTER(Delivery), P, C.POINTER(DeliveryHdr)], I),
     }
     optional = {"usn_set_frame_reader", "usn_ctx_create_group", "usn_ctx_replicas",
                 "usn_replica_select", "usn_replica_device", "usn_result_bytes_ep",
-                "usn_set_lists_async", "usn_lists_wait", "usn_result_release"}   # A/B builds of older ABI versions lack these
+                "usn_set_lists_async", "usn_lists_wait", "usn_result_release", "usn_delivery_bytes",
+                "usn_delivery_bind", "usn_deliver", "usn_deliver_info"}   # A/B builds of older ABI versions lack these
     for name, (args, res) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -157,7 +177,8 @@ EXPORTED = ["usn_abi_version", "usn_strerror", "usn_last_hip_error", "usn_ctx_cr
             "usn_event_elapsed_ms", "usn_stream_wait_event", "usn_classify_multi",
             "usn_bridge_set", "usn_table_build", "usn_set_frame_reader", "usn_ctx_create_group",
             "usn_ctx_replicas", "usn_replica_select", "usn_replica_device", "usn_set_lists_async",
-            "usn_lists_wait", "usn_result_release"]
+            "usn_lists_wait", "usn_result_release", "usn_delivery_bytes", "usn_delivery_bind",
+            "usn_deliver", "usn_deliver_info"]
 
 
 def check(rc, what=""):
@@ -407,6 +428,14 @@ class Ctx:
                                   C.byref(info)), "usn_finalize")
         return info
 
+    def deliver(self, batch: "DeviceBatch", result: "DeviceResult", delivery: "DeviceDelivery",
+                stream=None):
+        """Pack every receiver's output ring of a classified batch on the device
+        (usn_deliver): asynchronous on `stream`; after finalize() for a batch that
+        needs the host stage."""
+        check(self.L.usn_deliver(self.h, C.byref(batch.desc), C.byref(result.desc),
+                                 C.byref(delivery.desc), stream), "usn_deliver")
+
 
 class DeviceBatch:
     """Frames + lengths resident in HBM (one drained rx ring)."""
@@ -524,3 +553,67 @@ def expected_lists(dec: np.ndarray, n_ep: int) -> dict:
     cuts = np.flatnonzero(np.diff(sb)) + 1
     return {int(sb[g[0]]): order[g].astype(np.uint32) for g in np.split(np.arange(sb.size), cuts)
             if g.size}
+
+
+class DeviceDelivery:
+    """One usn_delivery: cap_slots output slots of `slot` bytes, their lens[] and
+    src[], the per-endpoint slot offsets and the header.  `poison` fills the
+    whole allocation first (tests: what the kernels did not write stays)."""
+
+    def __init__(self, ctx: Ctx, cap_slots: int, slot: int, poison: int | None = None):
+        self.ctx = ctx
+        self.cap = int(cap_slots)
+        self.slot = int(slot)
+        nbytes = ctx.L.usn_delivery_bytes(self.cap, self.slot)
+        if nbytes == 0:
+            raise UsnError("usn_delivery_bytes: bad capacity %d or slot %d" % (self.cap, self.slot))
+        self.buf = ctx.alloc(nbytes)
+        self.desc = Delivery()
+        check(ctx.L.usn_delivery_bind(self.buf.ptr, nbytes, self.cap, self.slot, C.byref(self.desc)),
+              "usn_delivery_bind")
+        if poison is not None:
+            check(ctx.L.usn_memset_d(ctx.h, self.buf.ptr, poison, nbytes, None), "usn_memset_d")
+            ctx.sync()
+
+    def info(self, stream=None, strict=True) -> DeliveryHdr:
+        """The header after the delivery on `stream` finished.  strict: raise on
+        USN_DV_OVERFLOW / USN_DV_LONG (USN_ERANGE); else return it with .status."""
+        h = DeliveryHdr()
+        rc = self.ctx.L.usn_deliver_info(self.ctx.h, C.byref(self.desc), stream, C.byref(h))
+        if strict or rc != USN_ERANGE:
+            check(rc, "usn_deliver_info")
+        h.status = rc
+        return h
+
+    def _get(self, ptr, dtype, count):
+        if count == 0:
+            return np.empty(0, dtype)
+        return self.buf.download(dtype, count, ptr - self.buf.ptr)
+
+    def ep_off(self) -> np.ndarray:
+        """ring of endpoint e = slots [ep_off[e], ep_off[e + 1])"""
+        return self._get(self.desc.ep_off, np.uint32, USN_MAX_ENDPOINTS + 1)
+
+    def lens(self, k0=0, k1=None) -> np.ndarray:
+        k1 = self.cap if k1 is None else k1
+        return self._get(self.desc.lens + 2 * k0, np.uint16, k1 - k0)
+
+    def src(self, k0=0, k1=None) -> np.ndarray:
+        k1 = self.cap if k1 is None else k1
+        return self._get(self.desc.src + 4 * k0, np.uint32, k1 - k0)
+
+    def slots(self, k0=0, k1=None) -> np.ndarray:
+        k1 = self.cap if k1 is None else k1
+        return self._get(self.desc.frames + self.slot * k0, np.uint8,
+                         (k1 - k0) * self.slot).reshape(k1 - k0, self.slot)
+
+    def ring(self, e: int):
+        """(src_idx, lens, bytes[k, slot]) of endpoint e's ring"""
+        off = self.ep_off()
+        k0, k1 = int(off[e]), int(off[e + 1])
+        return self.src(k0, k1), self.lens(k0, k1), self.slots(k0, k1)
+
+    def free(self):
+        if self.buf is not None:
+            self.buf.free()
+            self.buf = None
