@@ -459,6 +459,63 @@ int usn_deliver(usn_ctx *ctx, const usn_batch *b, const usn_result *r, usn_deliv
 int usn_deliver_info(usn_ctx *ctx, const usn_delivery *d, void *hip_stream,
                      usn_delivery_hdr *host_out);
 
+/* ---- packed delivery: the same rings, byte-compact --------------------------
+ * The receiver rule and the order are usn_deliver's; the output has no slots.
+ * The frames of output slot 0, 1, ... of all receivers lie back to back in
+ * `frames`: slot k's frame starts at frames + 16 * off16[k] and occupies
+ * ceil16(lens[k]) bytes, of which [len, ceil16(len)) are zero.  Endpoint e's
+ * frames are bytes [ep_boff[e], ep_boff[e+1]) (ep_boff is monotone over all
+ * ids; an id that receives nothing has an empty range).  When the delivery
+ * fits, every byte of frames[0, need_bytes) is written, so a copy of that
+ * range carries no stale data; nothing is truncated (no USN_DV_LONG).  This
+ * is the layout for mixed frame sizes (a pcap or byte stream, a byte ring):
+ * the region is need_bytes, not need x the largest slot.
+ *
+ * Overflow.  need > cap: USN_DV_OVERFLOW; hdr->need and ep_off are valid,
+ * need_bytes is 0 and nothing else is written.  need <= cap but need_bytes >
+ * cap_bytes: USN_DV_OVERFLOW_BYTES; src, lens, off16, ep_off, ep_boff and
+ * need_bytes are valid and complete (off16 saturates at 2^32 - 1, which only
+ * a need_bytes of 2^36 or more reaches) and no byte of `frames` is written.
+ *
+ * Every delivered frame must be readable over its first ceil16(len) bytes,
+ * not just over usn_batch.window, as for usn_deliver. */
+#define USN_HAS_DELIVER_PACKED 1
+#define USN_DV_OVERFLOW_BYTES 4u   /* need_bytes > cap_bytes: no frame byte was written */
+typedef struct {
+  uint32_t need, cap, flags, n_recv;   /* as usn_delivery_hdr */
+  uint64_t need_bytes, cap_bytes;      /* sum of ceil16(len) over delivered slots / the region's size */
+} usn_pdelivery_hdr;
+typedef struct {
+  uint8_t  *frames;    /* cap_bytes; slot k's frame at frames + 16 * off16[k] */
+  uint32_t *off16;     /* cap: start of slot k in 16-byte units */
+  uint16_t *lens;      /* cap */
+  uint32_t *src;       /* cap */
+  uint32_t *ep_off;    /* USN_MAX_ENDPOINTS + 1: slots of endpoint e = [ep_off[e], ep_off[e+1]) */
+  uint64_t *ep_boff;   /* USN_MAX_ENDPOINTS + 1: bytes of endpoint e = [ep_boff[e], ep_boff[e+1]) */
+  usn_pdelivery_hdr *hdr;   /* followed by the kernels' scratch */
+  uint64_t cap, cap_bytes;
+} usn_pdelivery;
+/* Bytes of a packed delivery of cap_slots slots and cap_bytes frame bytes: 0
+ * unless cap_slots is in [1, 2^32) and cap_bytes a non-zero multiple of 16 of
+ * at most 2^36 - 16 (off16 is 32 bits).  usn_pdelivery_bind carves device (or,
+ * for layout checks, host) memory of that size into 256-byte aligned arrays:
+ * USN_EINVAL for such arguments, USN_ERANGE when `bytes` is too small.  The
+ * scratch behind the header holds the tile prefix and, for the most tiles a
+ * delivery of cap_slots can have (cap_slots / USN_DELIVER_TILE +
+ * USN_MAX_ENDPOINTS + 1), the tiles' byte totals and bases. */
+size_t usn_pdelivery_bytes(uint64_t cap_slots, uint64_t cap_bytes);
+int usn_pdelivery_bind(void *dev_mem, size_t bytes, uint64_t cap_slots, uint64_t cap_bytes,
+                       usn_pdelivery *out);
+/* usn_deliver with the packed output: the same validation (without the slot
+ * rules), stream order, receiver table and return codes; no host
+ * synchronisation and no copy in the steady state. */
+int usn_deliver_packed(usn_ctx *ctx, const usn_batch *b, const usn_result *r, usn_pdelivery *d,
+                       void *hip_stream);
+/* Synchronises `hip_stream` and copies the header to the host: USN_ERANGE
+ * when either overflow flag is set (host_out is filled all the same). */
+int usn_deliver_packed_info(usn_ctx *ctx, const usn_pdelivery *d, void *hip_stream,
+                            usn_pdelivery_hdr *host_out);
+
 /* Forget the carried decision cache of one endpoint (last_pkt = None). */
 int usn_cache_clear(usn_ctx *ctx, uint16_t endpoint);
 

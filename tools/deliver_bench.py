@@ -10,8 +10,12 @@ Inputs, results and deliveries rotate over `--rounds` distinct device sets
 (> the 256 MiB Infinity Cache in all); deliver and copy alternate in blocks so
 both see the same neighbours.  Times are device events on the one stream.
 
+--packed times usn_deliver_packed (byte-compact rings) on the same calls next
+to two yardsticks: usn_deliver of the same rings at --slot (2048 for c3) and a
+device-to-device copy of need_bytes, the three alternating in blocks.
+
 usage: python tools/deliver_bench.py [--config c5] [--frames N] [--multi 2] [--rounds 2]
-                                     [--launches 120] [--slot 64] [--json out.json]
+                                     [--launches 120] [--slot 64] [--packed] [--json out.json]
 """
 import argparse
 import ctypes as C
@@ -35,6 +39,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--launches", type=int, default=120)
     ap.add_argument("--slot", type=int, default=64)
+    ap.add_argument("--packed", action="store_true")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     n, Q, R = a.frames, a.multi, a.rounds
@@ -53,6 +58,12 @@ def main():
     copy_dst = [[d.desc.frames for d in row] for row in dvs]
     hip = C.CDLL("libamdhip64.so")
     hip.hipMemcpyDtoDAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    if a.packed:
+        # a frame is delivered at most once here (the tool's configs flood nothing): n slots and
+        # the ring's sum of ceil16(len) bytes hold any delivery
+        room = [int(((c.lens.astype(np.int64) + 15) // 16 * 16).sum()) for c in cfgs]
+        pds = [[lib.DevicePackedDelivery(ctx, n, room[k]) for k in range(Q)] for _ in range(R)]
+        need_b = [0] * Q   # per ring, after the first delivery
 
     def classify(r):
         ctx.classify_multi(bs[r], rs[r], s)
@@ -64,6 +75,14 @@ def main():
     def copy(r):
         for k in range(Q):
             assert hip.hipMemcpyDtoDAsync(copy_dst[r][k], copy_src[r][k], n * a.slot, s) == 0
+
+    def deliver_packed(r):
+        for k in range(Q):
+            ctx.deliver_packed(bs[r][k], rs[r][k], pds[r][k], s)
+
+    def copy_packed(r):
+        for k in range(Q):
+            assert hip.hipMemcpyDtoDAsync(pds[r][k].desc.frames, copy_src[r][k], need_b[k], s) == 0
 
     def timed(fn, count, after=None):
         evs = [(ctx.event(), ctx.event()) for _ in range(count)]
@@ -97,9 +116,13 @@ def main():
             assert h.need == int(off[int(rs[r][k].summary()["n_ep"])]), "need differs from the endpoint bins"
             need += h.need if r == 0 else 0
     src0, len0, _ = dvs[0][0].ring(2)
-    assert np.array_equal(src0, rs[0][0].lists().get(2, np.zeros(0, np.uint32))) and (len0 == 64).all()
-    dl_us, cp_us = [], []
+    assert np.array_equal(src0, rs[0][0].lists().get(2, np.zeros(0, np.uint32)))
+    assert np.array_equal(len0, cfgs[0].lens[src0])
     block = 30
+    if a.packed:
+        return packed(a, ctx, s, cfgs, rs, pds, need_b, need, deliver, deliver_packed, copy_packed,
+                      timed, block)
+    dl_us, cp_us = [], []
     while len(dl_us) < a.launches:
         dl_us += timed(deliver, block)
         cp_us += timed(copy, block)
@@ -114,6 +137,56 @@ def main():
                d2d_copy_gbps=round(2 * frames * a.slot / cp / 1e3, 1),
                deliver_over_copy=round(dl / cp, 2), classify_lists_us=round(cl, 1),
                deliver_share_of_call=round(dl / (dl + cl), 3))
+    print(json.dumps(out), flush=True)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+    ctx.close()
+
+
+def stats(us, name):
+    return {name + "_us": round(statistics.median(us), 1), name + "_min_us": round(min(us), 1),
+            name + "_p90_us": round(float(np.percentile(us, 90)), 1)}
+
+
+def packed(a, ctx, s, cfgs, rs, pds, need_b, need, deliver, deliver_packed, copy_packed, timed, block):
+    """usn_deliver_packed against usn_deliver at --slot and a copy of need_bytes"""
+    n, Q, R = a.frames, a.multi, a.rounds
+    for r in range(R):
+        deliver_packed(r)
+        for k in range(Q):
+            h = pds[r][k].info(s)
+            off = rs[r][k].bin_off()
+            assert h.need == int(off[int(rs[r][k].summary()["n_ep"])]), "need differs from the endpoint bins"
+            if r == 0:
+                need_b[k] = int(h.need_bytes)
+    # ring 0's bytes against the lists: every frame padded to 16 behind the one before
+    lists, c = rs[0][0].lists(), cfgs[0]
+    idx = np.concatenate([lists[e] for e in sorted(lists) if e < int(rs[0][0].summary()["n_ep"])])
+    c16 = (c.lens[idx].astype(np.int64) + 15) // 16 * 16
+    assert np.array_equal(pds[0][0].src(0, idx.size), idx) and int(c16.sum()) == need_b[0]
+    assert np.array_equal(pds[0][0].off16(0, idx.size), (np.cumsum(c16) - c16) // 16)
+    k = idx.size - 1
+    f0 = int(idx[k]) * c.stride
+    assert np.array_equal(pds[0][0].bytes(need_b[0] - int(c16[k]), need_b[0])[:c.lens[idx[k]]],
+                          np.asarray(c.frames).reshape(-1)[f0:f0 + int(c.lens[idx[k]])])
+    for r in range(R):   # warm-up of the copy at its final size
+        copy_packed(r)
+    pk_us, dl_us, cp_us = [], [], []
+    while len(pk_us) < a.launches:
+        pk_us += timed(deliver_packed, block)
+        dl_us += timed(deliver, block)
+        cp_us += timed(copy_packed, block)
+    nb = sum(need_b)
+    out = dict(config=a.config, frames_per_call=n * Q, rings=Q, slot=a.slot, delivered_slots=need,
+               need_bytes=nb, need_x_slot_bytes=need * a.slot,
+               bytes_per_delivered_frame=round(nb / max(need, 1), 1), launches=len(pk_us))
+    out.update(stats(pk_us, "packed"))
+    out.update(stats(dl_us, "fixed_slot"))
+    out.update(stats(cp_us, "d2d_copy_need_bytes"))
+    out["packed_over_fixed_slot"] = round(out["packed_us"] / out["fixed_slot_us"], 2)
+    out["packed_over_copy"] = round(out["packed_us"] / out["d2d_copy_need_bytes_us"], 2)
+    out["packed_frame_gbps"] = round(2 * nb / out["packed_us"] / 1e3, 1)
     print(json.dumps(out), flush=True)
     if a.json:
         with open(a.json, "w") as fh:

@@ -3809,18 +3809,18 @@ static int upload_eptab(usn_ctx *c, Replica &R) {
   return USN_OK;
 }
 
-int usn_deliver(usn_ctx *c, const usn_batch *b, const usn_result *r, usn_delivery *d, void *stream) {
-  if (!c || !b || !r || !d) return USN_EINVAL;
-  if (!b->frames || !b->lens || !r->index || !r->bin_off || !r->summary || !r->decisions ||
-      !d->frames || !d->lens || !d->src || !d->ep_off || !d->hdr)
-    return USN_EINVAL;
-  if (b->n == 0 || b->n >= 0xFFFFFFFFull || r->n < b->n) return USN_EINVAL;
-  if ((b->stride == 0) == (b->offsets == nullptr)) return USN_EINVAL;
-  if (d->slot == 0 || d->slot % 16 != 0 || (b->stride && d->slot < b->stride)) return USN_EINVAL;
-  if (d->cap == 0 || d->cap > 0xFFFFFFFFull || b->src_endpoint >= USN_MAX_ENDPOINTS) return USN_EINVAL;
-  if ((((uintptr_t)b->frames | (uintptr_t)d->frames) & 15) != 0 || (b->stride & 15) != 0) return USN_EINVAL;
-  if (c->reps.empty()) return USN_ENODEV;
-  std::lock_guard<std::mutex> g(c->mu);
+/* what usn_deliver and usn_deliver_packed ask of the batch and the result */
+static bool deliver_inputs_ok(const usn_batch *b, const usn_result *r) {
+  if (!b->frames || !b->lens || !r->index || !r->bin_off || !r->summary || !r->decisions) return false;
+  if (b->n == 0 || b->n >= 0xFFFFFFFFull || r->n < b->n) return false;
+  if ((b->stride == 0) == (b->offsets == nullptr)) return false;
+  if (b->src_endpoint >= USN_MAX_ENDPOINTS) return false;
+  return ((uintptr_t)b->frames & 15) == 0 && (b->stride & 15) == 0;
+}
+
+/* With c->mu held: the replica that classified into r (*Rp), its receiver
+ * table at today's endpoint set, and `stream` ordered after r's lists */
+static int deliver_order(usn_ctx *c, const usn_result *r, void *stream, Replica **Rp) {
   for (const usn_ctx::Tx &t : c->txq)
     if (t.decisions == r->decisions) return USN_EBUSY;   // lists not final before its usn_finalize
   const auto br = c->batch_rep.find(r->decisions);
@@ -3831,6 +3831,21 @@ int usn_deliver(usn_ctx *c, const usn_batch *b, const usn_result *r, usn_deliver
   const auto le = c->lists_ev.find(r->decisions);        // lists built on the side stream
   if (le != c->lists_ev.end() && le->second.ev)
     HIPCHK(hipStreamWaitEvent((hipStream_t)stream, le->second.ev, 0));
+  *Rp = &R;
+  return USN_OK;
+}
+
+int usn_deliver(usn_ctx *c, const usn_batch *b, const usn_result *r, usn_delivery *d, void *stream) {
+  if (!c || !b || !r || !d) return USN_EINVAL;
+  if (!d->frames || !d->lens || !d->src || !d->ep_off || !d->hdr || !deliver_inputs_ok(b, r))
+    return USN_EINVAL;
+  if (d->slot == 0 || d->slot % 16 != 0 || (b->stride && d->slot < b->stride)) return USN_EINVAL;
+  if (d->cap == 0 || d->cap > 0xFFFFFFFFull || ((uintptr_t)d->frames & 15) != 0) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  std::lock_guard<std::mutex> g(c->mu);
+  Replica *Rp = nullptr;
+  { int s = deliver_order(c, r, stream, &Rp); if (s) return s; }
+  Replica &R = *Rp;
   usn::DeliverArgs a;
   std::memset(&a, 0, sizeof a);
   a.frames = b->frames;
@@ -3863,6 +3878,100 @@ int usn_deliver_info(usn_ctx *c, const usn_delivery *d, void *stream, usn_delive
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   HIPCHK(hipMemcpy(out, d->hdr, sizeof *out, hipMemcpyDeviceToHost));
   return out->flags & (USN_DV_OVERFLOW | USN_DV_LONG) ? USN_ERANGE : USN_OK;
+}
+
+/* ---- packed delivery: byte-compact rings (usn_deliver_packed.hip) ----------- */
+struct PDeliveryLayout {
+  size_t frames, off16, lens, src, ep_off, ep_boff, hdr, total;
+};
+static bool pdelivery_layout(uint64_t cap, uint64_t cap_bytes, PDeliveryLayout &L) {
+  if (cap == 0 || cap > 0xFFFFFFFFull) return false;
+  if (cap_bytes == 0 || cap_bytes % 16 != 0 || cap_bytes > (1ull << 36) - 16) return false;   // off16 is 32 bits
+  size_t off = 0;
+  L.frames = off; off = align256(off + (size_t)cap_bytes);
+  L.off16 = off; off = align256(off + (size_t)cap * 4);
+  L.lens = off; off = align256(off + (size_t)cap * 2);
+  L.src = off; off = align256(off + (size_t)cap * 4);
+  L.ep_off = off; off = align256(off + (size_t)USN_DT_IDS * 4);
+  L.ep_boff = off; off = align256(off + (size_t)USN_DT_IDS * 8);
+  L.hdr = off; off = align256(off + usn::DELIVER_SCRATCH_OFF + usn::pdeliver_scratch_bytes(cap));
+  L.total = off;
+  return true;
+}
+
+size_t usn_pdelivery_bytes(uint64_t cap_slots, uint64_t cap_bytes) {
+  PDeliveryLayout L;
+  return pdelivery_layout(cap_slots, cap_bytes, L) ? L.total : 0;
+}
+
+int usn_pdelivery_bind(void *mem, size_t bytes, uint64_t cap_slots, uint64_t cap_bytes, usn_pdelivery *out) {
+  PDeliveryLayout L;
+  if (!mem || !out || ((uintptr_t)mem & 15) != 0 || !pdelivery_layout(cap_slots, cap_bytes, L)) return USN_EINVAL;
+  if (bytes < L.total) return USN_ERANGE;
+  uint8_t *b = static_cast<uint8_t *>(mem);
+  out->frames = b + L.frames;
+  out->off16 = reinterpret_cast<uint32_t *>(b + L.off16);
+  out->lens = reinterpret_cast<uint16_t *>(b + L.lens);
+  out->src = reinterpret_cast<uint32_t *>(b + L.src);
+  out->ep_off = reinterpret_cast<uint32_t *>(b + L.ep_off);
+  out->ep_boff = reinterpret_cast<uint64_t *>(b + L.ep_boff);
+  out->hdr = reinterpret_cast<usn_pdelivery_hdr *>(b + L.hdr);
+  out->cap = cap_slots;
+  out->cap_bytes = cap_bytes;
+  return USN_OK;
+}
+
+int usn_deliver_packed(usn_ctx *c, const usn_batch *b, const usn_result *r, usn_pdelivery *d, void *stream) {
+  if (!c || !b || !r || !d) return USN_EINVAL;
+  if (!d->frames || !d->off16 || !d->lens || !d->src || !d->ep_off || !d->ep_boff || !d->hdr ||
+      !deliver_inputs_ok(b, r))
+    return USN_EINVAL;
+  if (d->cap == 0 || d->cap > 0xFFFFFFFFull || d->cap_bytes == 0 || d->cap_bytes % 16 != 0 ||
+      d->cap_bytes > (1ull << 36) - 16)
+    return USN_EINVAL;
+  if ((((uintptr_t)d->frames | (uintptr_t)d->ep_boff | (uintptr_t)d->hdr) & 15) != 0) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  std::lock_guard<std::mutex> g(c->mu);
+  Replica *Rp = nullptr;
+  { int s = deliver_order(c, r, stream, &Rp); if (s) return s; }
+  Replica &R = *Rp;
+  usn::PackedDeliverArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.frames = b->frames;
+  a.stride = b->stride;
+  a.offsets = b->offsets;
+  a.lens = b->lens;
+  a.n = (uint32_t)b->n;
+  a.src = b->src_endpoint;
+  a.index = r->index;
+  a.bin_off = r->bin_off;
+  a.summary = r->summary;
+  a.eptab = R.d_eptab;
+  a.out_frames = d->frames;
+  a.out_off16 = d->off16;
+  a.out_lens = d->lens;
+  a.out_src = d->src;
+  a.ep_off = d->ep_off;
+  a.ep_boff = d->ep_boff;
+  a.hdr = d->hdr;
+  uint8_t *scratch = reinterpret_cast<uint8_t *>(d->hdr);
+  a.tile_pfx = reinterpret_cast<uint32_t *>(scratch + usn::DELIVER_SCRATCH_OFF);
+  a.tile_base = reinterpret_cast<uint64_t *>(scratch + usn::PDELIVER_BASE_OFF);
+  a.tile_b16 = reinterpret_cast<uint32_t *>(a.tile_base + usn::pdeliver_max_tiles(d->cap));
+  a.cap = (uint32_t)d->cap;
+  a.cap_bytes = d->cap_bytes;
+  // the merge and copy grids: what the device holds at once, as usn_deliver's pack grid
+  HIPCHK(usn::launch_deliver_packed(a, (uint32_t)std::max(R.n_cu, 1) * 8u, (hipStream_t)stream));
+  if (c->sel < c->reps.size() && c->reps[c->sel].device != R.device) HIPCHK(hipSetDevice(c->device));
+  return USN_OK;
+}
+
+int usn_deliver_packed_info(usn_ctx *c, const usn_pdelivery *d, void *stream, usn_pdelivery_hdr *out) {
+  if (!c || !d || !d->hdr || !out) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  HIPCHK(hipMemcpy(out, d->hdr, sizeof *out, hipMemcpyDeviceToHost));
+  return out->flags & (USN_DV_OVERFLOW | USN_DV_OVERFLOW_BYTES) ? USN_ERANGE : USN_OK;
 }
 
 /* ---- device plumbing ------------------------------------------------------- */

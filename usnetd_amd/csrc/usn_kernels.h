@@ -277,6 +277,53 @@ constexpr size_t DELIVER_SCRATCH_OFF = 256;
 constexpr size_t DELIVER_SCRATCH_BYTES = (size_t)USN_DT_IDS * 4;
 hipError_t launch_deliver(const DeliverArgs &a, uint32_t pack_grid, hipStream_t stream);
 
+/* ---- packed delivery (usn_deliver_packed.hip): byte-compact rings ----------
+ * Four launches on the caller's stream, same receivers, order and tiles:
+ *   pdeliver_plan_kernel   the plan above, plus need_bytes = 0 and cap_bytes
+ *   pdeliver_merge_kernel  device-sized grid: per tile the cut and the merge,
+ *                          src[] / lens[], and the tile's 16-byte pieces
+ *                          (sum of ceil16(len) / 16) into tile_b16[t]
+ *   pdeliver_scan_kernel   one workgroup: exclusive 64-bit scan of tile_b16 in
+ *                          blocks of PDELIVER_SCAN_BLOCK tiles (tile_base),
+ *                          ep_boff, need_bytes, the byte-overflow flag
+ *   pdeliver_copy_kernel   device-sized grid: per tile src[] / lens[] read
+ *                          back, the pieces' scan in LDS, off16[], and the
+ *                          output-stationary gather (lane i of the tile's
+ *                          pieces i, i + 256, ...) */
+struct PackedDeliverArgs {
+  const uint8_t *frames;
+  uint64_t stride;
+  const uint64_t *offsets;
+  const uint16_t *lens;
+  uint32_t n;               /* frames in the batch (< 2^32 - 1) */
+  uint32_t src;             /* the batch's source endpoint */
+  const uint32_t *index;
+  const uint32_t *bin_off;
+  const usn_summary *summary;
+  const uint16_t *eptab;    /* as DeliverArgs */
+  uint8_t *out_frames;
+  uint32_t *out_off16;
+  uint16_t *out_lens;
+  uint32_t *out_src;
+  uint32_t *ep_off;         /* [USN_DT_IDS] */
+  uint64_t *ep_boff;        /* [USN_DT_IDS] */
+  usn_pdelivery_hdr *hdr;
+  uint32_t *tile_pfx;       /* [USN_DT_IDS], as DeliverArgs */
+  uint64_t *tile_base;      /* [max tiles]: 16-byte pieces before tile t */
+  uint32_t *tile_b16;       /* [max tiles]: 16-byte pieces of tile t (<= P * 4096) */
+  uint32_t cap;
+  uint64_t cap_bytes;
+};
+constexpr uint32_t PDELIVER_SCAN_BLOCK = 1024;   /* tiles per pass of the tile scan */
+/* the most tiles a delivery of cap slots has: a receiver's last tile may be short */
+constexpr size_t pdeliver_max_tiles(uint64_t cap) { return (size_t)(cap / USN_DELIVER_TILE) + USN_DT_IDS; }
+/* scratch behind usn_pdelivery.hdr, from DELIVER_SCRATCH_OFF: tile_pfx, tile_base, tile_b16 */
+constexpr size_t PDELIVER_BASE_OFF = DELIVER_SCRATCH_OFF + DELIVER_SCRATCH_BYTES;   /* 8-byte aligned */
+constexpr size_t pdeliver_scratch_bytes(uint64_t cap) {
+  return DELIVER_SCRATCH_BYTES + pdeliver_max_tiles(cap) * 12;
+}
+hipError_t launch_deliver_packed(const PackedDeliverArgs &a, uint32_t grid, hipStream_t stream);
+
 }  // namespace usn
 
 /* the same kernels at 512 threads per tile (a second compilation of

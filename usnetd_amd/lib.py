@@ -25,6 +25,7 @@ USN_MAX_ENDPOINTS = 4095
 USN_MAX_BINS = USN_MAX_ENDPOINTS + 3
 USN_DELIVER_TILE = 512   # output slots per pack tile of usn_deliver (usn_classify.h)
 DV_OVERFLOW, DV_LONG = 1, 2
+DV_OVERFLOW_BYTES = 4   # usn_deliver_packed: need_bytes > cap_bytes
 R_WINDOW = 7
 PARITY_MASK = 0x00FFFFFF
 EP_NIC, EP_HOST, EP_PIPE, EP_UDS = 0, 1, 2, 3
@@ -83,6 +84,17 @@ class Delivery(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("lens", C.c_void_p), ("src", C.c_void_p),
                 ("ep_off", C.c_void_p), ("hdr", C.c_void_p), ("cap", C.c_uint64),
                 ("slot", C.c_uint32), ("_r", C.c_uint32)]
+
+
+class PDeliveryHdr(C.Structure):
+    _fields_ = [("need", C.c_uint32), ("cap", C.c_uint32), ("flags", C.c_uint32),
+                ("n_recv", C.c_uint32), ("need_bytes", C.c_uint64), ("cap_bytes", C.c_uint64)]
+
+
+class PDelivery(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("off16", C.c_void_p), ("lens", C.c_void_p),
+                ("src", C.c_void_p), ("ep_off", C.c_void_p), ("ep_boff", C.c_void_p),
+                ("hdr", C.c_void_p), ("cap", C.c_uint64), ("cap_bytes", C.c_uint64)]
 
 
 TILE_HDR_DTYPE = np.dtype([("n_frames", "<u2"), ("_r0", "<u2"), ("n_host", "<u2"),
@@ -151,11 +163,16 @@ def load(path: str | None = None):
         "usn_delivery_bind": ([P, SZ, U64, U32, C.POINTER(Delivery)], I),
         "usn_deliver": ([P, C.POINTER(Batch), C.POINTER(Result), C.POINTER(Delivery), P], I),
         "usn_deliver_info": ([P, C.POINTER(Delivery), P, C.POINTER(DeliveryHdr)], I),
+        "usn_pdelivery_bytes": ([U64, U64], SZ),
+        "usn_pdelivery_bind": ([P, SZ, U64, U64, C.POINTER(PDelivery)], I),
+        "usn_deliver_packed": ([P, C.POINTER(Batch), C.POINTER(Result), C.POINTER(PDelivery), P], I),
+        "usn_deliver_packed_info": ([P, C.POINTER(PDelivery), P, C.POINTER(PDeliveryHdr)], I),
     }
     optional = {"usn_set_frame_reader", "usn_ctx_create_group", "usn_ctx_replicas",
                 "usn_replica_select", "usn_replica_device", "usn_result_bytes_ep",
                 "usn_set_lists_async", "usn_lists_wait", "usn_result_release", "usn_delivery_bytes",
-                "usn_delivery_bind", "usn_deliver", "usn_deliver_info"}   # A/B builds of older ABI versions lack these
+                "usn_delivery_bind", "usn_deliver", "usn_deliver_info", "usn_pdelivery_bytes",
+                "usn_pdelivery_bind", "usn_deliver_packed", "usn_deliver_packed_info"}   # A/B builds of older ABI versions lack these
     for name, (args, res) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -178,7 +195,8 @@ EXPORTED = ["usn_abi_version", "usn_strerror", "usn_last_hip_error", "usn_ctx_cr
             "usn_bridge_set", "usn_table_build", "usn_set_frame_reader", "usn_ctx_create_group",
             "usn_ctx_replicas", "usn_replica_select", "usn_replica_device", "usn_set_lists_async",
             "usn_lists_wait", "usn_result_release", "usn_delivery_bytes", "usn_delivery_bind",
-            "usn_deliver", "usn_deliver_info"]
+            "usn_deliver", "usn_deliver_info", "usn_pdelivery_bytes", "usn_pdelivery_bind",
+            "usn_deliver_packed", "usn_deliver_packed_info"]
 
 
 def check(rc, what=""):
@@ -436,6 +454,13 @@ class Ctx:
         check(self.L.usn_deliver(self.h, C.byref(batch.desc), C.byref(result.desc),
                                  C.byref(delivery.desc), stream), "usn_deliver")
 
+    def deliver_packed(self, batch: "DeviceBatch", result: "DeviceResult",
+                       delivery: "DevicePackedDelivery", stream=None):
+        """deliver() with byte-compact rings (usn_deliver_packed): every frame
+        behind the one before it, padded to 16 bytes."""
+        check(self.L.usn_deliver_packed(self.h, C.byref(batch.desc), C.byref(result.desc),
+                                        C.byref(delivery.desc), stream), "usn_deliver_packed")
+
 
 class DeviceBatch:
     """Frames + lengths resident in HBM (one drained rx ring)."""
@@ -612,6 +637,70 @@ class DeviceDelivery:
         off = self.ep_off()
         k0, k1 = int(off[e]), int(off[e + 1])
         return self.src(k0, k1), self.lens(k0, k1), self.slots(k0, k1)
+
+    def free(self):
+        if self.buf is not None:
+            self.buf.free()
+            self.buf = None
+
+
+class DevicePackedDelivery:
+    """One usn_pdelivery: cap_bytes of frames lying back to back (each padded to
+    16 bytes), off16[] / lens[] / src[] per slot, the per-endpoint slot and byte
+    offsets and the header.  `poison` as for DeviceDelivery."""
+
+    def __init__(self, ctx: Ctx, cap_slots: int, cap_bytes: int, poison: int | None = None):
+        self.ctx = ctx
+        self.cap = int(cap_slots)
+        self.cap_bytes = int(cap_bytes)
+        nbytes = ctx.L.usn_pdelivery_bytes(self.cap, self.cap_bytes)
+        if nbytes == 0:
+            raise UsnError("usn_pdelivery_bytes: bad capacity %d slots / %d bytes" % (self.cap, self.cap_bytes))
+        self.buf = ctx.alloc(nbytes)
+        self.desc = PDelivery()
+        check(ctx.L.usn_pdelivery_bind(self.buf.ptr, nbytes, self.cap, self.cap_bytes,
+                                       C.byref(self.desc)), "usn_pdelivery_bind")
+        if poison is not None:
+            check(ctx.L.usn_memset_d(ctx.h, self.buf.ptr, poison, nbytes, None), "usn_memset_d")
+            ctx.sync()
+
+    def info(self, stream=None, strict=True) -> PDeliveryHdr:
+        """The header after the delivery on `stream` finished.  strict: raise on
+        either overflow flag (USN_ERANGE); else return it with .status."""
+        h = PDeliveryHdr()
+        rc = self.ctx.L.usn_deliver_packed_info(self.ctx.h, C.byref(self.desc), stream, C.byref(h))
+        if strict or rc != USN_ERANGE:
+            check(rc, "usn_deliver_packed_info")
+        h.status = rc
+        return h
+
+    _get = DeviceDelivery._get
+
+    def ep_off(self) -> np.ndarray:
+        """slots of endpoint e = [ep_off[e], ep_off[e + 1])"""
+        return self._get(self.desc.ep_off, np.uint32, USN_MAX_ENDPOINTS + 1)
+
+    def ep_boff(self) -> np.ndarray:
+        """bytes of endpoint e = [ep_boff[e], ep_boff[e + 1])"""
+        return self._get(self.desc.ep_boff, np.uint64, USN_MAX_ENDPOINTS + 1)
+
+    def src(self, k0=0, k1=None) -> np.ndarray:
+        k1 = self.cap if k1 is None else k1
+        return self._get(self.desc.src + 4 * k0, np.uint32, k1 - k0)
+
+    def lens(self, k0=0, k1=None) -> np.ndarray:
+        k1 = self.cap if k1 is None else k1
+        return self._get(self.desc.lens + 2 * k0, np.uint16, k1 - k0)
+
+    def off16(self, k0=0, k1=None) -> np.ndarray:
+        """start of slot k's frame in 16-byte units"""
+        k1 = self.cap if k1 is None else k1
+        return self._get(self.desc.off16 + 4 * k0, np.uint32, k1 - k0)
+
+    def bytes(self, b0=0, b1=None) -> np.ndarray:
+        """frames[b0, b1) (default: the whole region of cap_bytes)"""
+        b1 = self.cap_bytes if b1 is None else b1
+        return self._get(self.desc.frames + b0, np.uint8, b1 - b0)
 
     def free(self):
         if self.buf is not None:
