@@ -516,6 +516,55 @@ int usn_deliver_packed(usn_ctx *ctx, const usn_batch *b, const usn_result *r, us
 int usn_deliver_packed_info(usn_ctx *ctx, const usn_pdelivery *d, void *hip_stream,
                             usn_pdelivery_hdr *host_out);
 
+/* ---- round delivery: one ring per endpoint for a whole poll round -----------
+ * The reference drains every readable endpoint in one poll round and writes
+ * each frame straight into its target's ring, so after a round endpoint e
+ * holds ONE ring: source 0's frames for it, then source 1's, and so on.
+ * usn_deliver_round packs that ring for up to USN_ROUND_MAX drained rings
+ * b[k] classified into r[k], k = 0 .. count - 1 in poll order (the order
+ * usn_classify_multi took them; they need not come from one classify call,
+ * and sources may repeat: consecutive tx rings of a sender, consecutive
+ * drains of a NIC).  Every result must be final.
+ *
+ * Segment (e, k) is exactly what usn_deliver(b[k], r[k]) gives receiver e:
+ * the receiver rule, the order, the slot bytes, the zeroed tail up to
+ * ceil16(len), the truncation and USN_DV_LONG.  It occupies slots
+ * [seg_off[8e + k], seg_off[8e + k + 1]); rings k >= count are empty.
+ * ep_off[e] = seg_off[8e], and endpoint e's round ring [ep_off[e],
+ * ep_off[e+1]) is its segments back to back.  src[] holds the frame index
+ * inside the slot's own ring; the ring follows from seg_off.  need is the sum
+ * over the rings of usn_deliver's need; n_recv counts receivers whose round
+ * ring is not empty.  need > cap: USN_DV_OVERFLOW, no slot and no src / lens
+ * entry is written; need, ep_off and seg_off stay valid. */
+#define USN_HAS_DELIVER_ROUND 1
+#define USN_ROUND_MAX 8
+typedef struct {            /* usn_delivery's arrays, plus the segments */
+  uint8_t *frames;
+  uint16_t *lens;
+  uint32_t *src;
+  uint32_t *ep_off;
+  uint32_t *seg_off;        /* USN_ROUND_MAX * (USN_MAX_ENDPOINTS + 1) + 1 */
+  usn_delivery_hdr *hdr;    /* followed by the kernels' scratch */
+  uint64_t cap;
+  uint32_t slot, _r;
+} usn_rdelivery;
+/* As usn_delivery_bytes / usn_delivery_bind, with room for seg_off. */
+size_t usn_rdelivery_bytes(uint64_t cap_slots, uint32_t slot);
+int usn_rdelivery_bind(void *dev_mem, size_t bytes, uint64_t cap_slots, uint32_t slot,
+                       usn_rdelivery *out);
+/* Two launches on `hip_stream` whatever count is, ordered after every
+ * result's lists; usn_deliver's validation holds for each ring (the slot
+ * rules against each strided ring's stride), the receiver table is uploaded
+ * once, and the steady state has no host synchronisation and no copy.
+ * USN_EINVAL: count 0 or above USN_ROUND_MAX, what usn_deliver refuses for
+ * any ring, results classified on different replicas; USN_EBUSY: an r[k] of a
+ * tx batch not yet finalized; USN_ENODEV: a USN_HOST_ONLY context. */
+int usn_deliver_round(usn_ctx *ctx, const usn_batch *b, const usn_result *r, uint32_t count,
+                      usn_rdelivery *d, void *hip_stream);
+/* As usn_deliver_info. */
+int usn_deliver_round_info(usn_ctx *ctx, const usn_rdelivery *d, void *hip_stream,
+                           usn_delivery_hdr *host_out);
+
 /* Forget the carried decision cache of one endpoint (last_pkt = None). */
 int usn_cache_clear(usn_ctx *ctx, uint16_t endpoint);
 

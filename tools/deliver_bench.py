@@ -14,8 +14,14 @@ both see the same neighbours.  Times are device events on the one stream.
 to two yardsticks: usn_deliver of the same rings at --slot (2048 for c3) and a
 device-to-device copy of need_bytes, the three alternating in blocks.
 
+--round times usn_deliver_round (the call's rings as one poll round: one ring
+per endpoint, two launches) next to the loop of --multi usn_deliver calls on
+the same rings and results, and to ONE device-to-device copy of the same
+need x slot bytes, the three alternating in blocks.
+
 usage: python tools/deliver_bench.py [--config c5] [--frames N] [--multi 2] [--rounds 2]
-                                     [--launches 120] [--slot 64] [--packed] [--json out.json]
+                                     [--launches 120] [--slot 64] [--packed | --round]
+                                     [--json out.json]
 """
 import argparse
 import ctypes as C
@@ -40,6 +46,7 @@ def main():
     ap.add_argument("--launches", type=int, default=120)
     ap.add_argument("--slot", type=int, default=64)
     ap.add_argument("--packed", action="store_true")
+    ap.add_argument("--round", action="store_true")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     n, Q, R = a.frames, a.multi, a.rounds
@@ -122,6 +129,8 @@ def main():
     if a.packed:
         return packed(a, ctx, s, cfgs, rs, pds, need_b, need, deliver, deliver_packed, copy_packed,
                       timed, block)
+    if a.round:
+        return round_mode(a, ctx, s, hip, bs, rs, dvs, need, deliver, timed, block)
     dl_us, cp_us = [], []
     while len(dl_us) < a.launches:
         dl_us += timed(deliver, block)
@@ -147,6 +156,50 @@ def main():
 def stats(us, name):
     return {name + "_us": round(statistics.median(us), 1), name + "_min_us": round(min(us), 1),
             name + "_p90_us": round(float(np.percentile(us, 90)), 1)}
+
+
+def round_mode(a, ctx, s, hip, bs, rs, dvs, need, deliver, timed, block):
+    """usn_deliver_round against the loop of usn_deliver calls and one copy of need x slot bytes"""
+    n, Q, R = a.frames, a.multi, a.rounds
+    rds = [lib.DeviceRoundDelivery(ctx, n * Q, a.slot) for _ in range(R)]
+    cp_src = ctx.alloc(need * a.slot)
+
+    def deliver_round(r):
+        ctx.deliver_round(bs[r], rs[r], rds[r], s)
+
+    def copy_round(r):
+        assert hip.hipMemcpyDtoDAsync(rds[r].desc.frames, cp_src.ptr, need * a.slot, s) == 0
+
+    for r in list(range(R)) * 2:   # warm-up, and what the round holds against the per-ring deliveries
+        deliver_round(r)
+        copy_round(r)
+    deliver(0)
+    deliver_round(0)
+    assert rds[0].info(s).need == need, "need differs from the sum of the rings' needs"
+    for e in (2, int(rs[0][0].summary()["n_ep"]) - 1):
+        src, lens, slots, ring = rds[0].ring(e)
+        per = [dvs[0][k].ring(e) for k in range(Q)]
+        assert np.array_equal(ring, np.repeat(np.arange(Q), [p[0].size for p in per]))
+        for i, got in enumerate((src, lens, slots)):
+            assert np.array_equal(got, np.concatenate([p[i] for p in per])), "round ring differs from its segments"
+    rd_us, lp_us, cp_us = [], [], []
+    while len(rd_us) < a.launches:
+        rd_us += timed(deliver_round, block)
+        lp_us += timed(deliver, block)
+        cp_us += timed(copy_round, block)
+    out = dict(config=a.config, frames_per_call=n * Q, rings=Q, slot=a.slot, delivered_slots=need,
+               launches=len(rd_us), launches_per_call_round=2, launches_per_call_loop=2 * Q)
+    out.update(stats(rd_us, "round"))
+    out.update(stats(lp_us, "deliver_loop"))
+    out.update(stats(cp_us, "d2d_copy"))
+    out["round_over_loop"] = round(out["round_us"] / out["deliver_loop_us"], 3)
+    out["round_over_copy"] = round(out["round_us"] / out["d2d_copy_us"], 2)
+    out["loop_over_copy"] = round(out["deliver_loop_us"] / out["d2d_copy_us"], 2)
+    print(json.dumps(out), flush=True)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+    ctx.close()
 
 
 def packed(a, ctx, s, cfgs, rs, pds, need_b, need, deliver, deliver_packed, copy_packed, timed, block):

@@ -1,9 +1,10 @@
 /*
- * usn_deliver_common.h -- what the two delivery modes share (usn_deliver.hip:
- * fixed slots, usn_deliver_packed.hip: byte-compact): the receiver rule, the
- * plan over the 4096 endpoint ids, a tile's receiver, the three-list cut and
- * the rank merge in LDS.  Device code only; A is DeliverArgs or
- * PackedDeliverArgs (the fields used here have the same names in both).
+ * usn_deliver_common.h -- what the delivery modes share (usn_deliver.hip: fixed
+ * slots, usn_deliver_packed.hip: byte-compact, usn_deliver_round.hip: a poll
+ * round's rings in one): the receiver rule, the plan over the 4096 endpoint
+ * ids, a tile's receiver, the three-list cut and the rank merge in LDS.  Device
+ * code only; A is DeliverArgs or PackedDeliverArgs (the fields used here have
+ * the same names in both) or, for recv_lists, one ring of a round.
  */
 #ifndef USN_DELIVER_COMMON_H
 #define USN_DELIVER_COMMON_H
@@ -143,38 +144,33 @@ __device__ __forceinline__ uint32_t tile_receiver(const uint32_t *tile_pfx, uint
 /* what wave 0 hands the workgroup per tile */
 enum { H_M = 0, H_OUT0 = 1, H_CUT = 2, H_RL = 5, H_WORDS = 8 };
 
-/* Wave 0: tile t's receiver, the cut of its up to three sorted, disjoint lists
- * at the tile's first merged position k0, and what follows the cuts: s_h[H_M]
- * slots from output slot s_h[H_OUT0], run r = s_h[H_RL + r] entries of index[]
- * from position s_h[H_CUT + r]. */
-template <class A>
-__device__ __forceinline__ void tile_cut(const A &a, uint32_t t, uint32_t n_ep, uint32_t nic,
-                                         uint32_t lane, uint32_t *s_h) {
-  const uint32_t e = tile_receiver(a.tile_pfx, t, lane);
-  uint32_t lo[3], hi[3], len[3], x[3] = {0, 0, 0};
-  recv_lists(a, e, n_ep, nic, lo, hi);
-  for (int r = 0; r < 3; ++r) len[r] = hi[r] - lo[r];
+/* One whole wave: the cuts x[r] of three sorted, disjoint lists (list r =
+ * len[r] entries of index[] from position lo[r], entries below n) at merged
+ * position k0 <= len[0] + len[1] + len[2]: x[0] + x[1] + x[2] == k0 and every
+ * entry before a cut lies below every entry after one.  k0 need not be a
+ * multiple of the tile. */
+__device__ __forceinline__ void lists_cut(const uint32_t *index, uint32_t n, const uint32_t lo[3],
+                                          const uint32_t len[3], uint32_t k0, uint32_t lane,
+                                          uint32_t x[3]) {
   const uint32_t total = len[0] + len[1] + len[2];
-  const uint32_t k0 = (t - a.tile_pfx[e]) * P;   // < total
+  for (int r = 0; r < 3; ++r) x[r] = 0;
   if (k0 > 0 && (len[0] == total || len[1] == total || len[2] == total)) {
     for (int r = 0; r < 3; ++r) x[r] = len[r] ? k0 : 0u;   // one list: nothing to search
   } else if (k0 > 0) {
-    /* cuts x[r], x[0] + x[1] + x[2] == k0, every entry before a cut below
-     * every entry after one.  x[r] lies in [xmin, xmax] whatever the
-     * entries are; the k0-th merged entry v* lies above list r's entry
-     * xmin - 1 and not above its entry k0 */
+    /* x[r] lies in [xmin, xmax] whatever the entries are; the k0-th merged
+     * entry v* lies above list r's entry xmin - 1 and not above its entry k0 */
     uint32_t xmin[3], xmax[3];
-    unsigned long long L = 0, H = a.n;
+    unsigned long long L = 0, H = n;
     for (int r = 0; r < 3; ++r) {
       const uint32_t others = total - len[r];
       xmin[r] = k0 > others ? k0 - others : 0u;
       xmax[r] = k0 < len[r] ? k0 : len[r];
       if (xmin[r] >= 1) {
-        const unsigned long long v = (unsigned long long)a.index[lo[r] + xmin[r] - 1] + 1;
+        const unsigned long long v = (unsigned long long)index[lo[r] + xmin[r] - 1] + 1;
         L = v > L ? v : L;
       }
       if (k0 < len[r]) {
-        const unsigned long long v = a.index[lo[r] + k0];
+        const unsigned long long v = index[lo[r] + k0];
         H = v < H ? v : H;
       }
     }
@@ -185,7 +181,7 @@ __device__ __forceinline__ void tile_cut(const A &a, uint32_t t, uint32_t n_ep, 
       const unsigned long long cand = L + ((span * lane) >> 6);
       uint32_t f = 0;
       for (int r = 0; r < 3; ++r)
-        f += lbound(a.index, lo[r] + xmin[r], lo[r] + xmax[r], cand) - lo[r];
+        f += lbound(index, lo[r] + xmin[r], lo[r] + xmax[r], cand) - lo[r];
       const unsigned long long ok = __ballot(f >= k0);
       if (ok == 0) {
         L = L + ((span * 63u) >> 6) + 1;
@@ -196,8 +192,24 @@ __device__ __forceinline__ void tile_cut(const A &a, uint32_t t, uint32_t n_ep, 
       }
     }
     for (int r = 0; r < 3; ++r)
-      x[r] = lbound(a.index, lo[r] + xmin[r], lo[r] + xmax[r], L) - lo[r];
+      x[r] = lbound(index, lo[r] + xmin[r], lo[r] + xmax[r], L) - lo[r];
   }
+}
+
+/* Wave 0: tile t's receiver, the cut of its up to three sorted, disjoint lists
+ * at the tile's first merged position k0, and what follows the cuts: s_h[H_M]
+ * slots from output slot s_h[H_OUT0], run r = s_h[H_RL + r] entries of index[]
+ * from position s_h[H_CUT + r]. */
+template <class A>
+__device__ __forceinline__ void tile_cut(const A &a, uint32_t t, uint32_t n_ep, uint32_t nic,
+                                         uint32_t lane, uint32_t *s_h) {
+  const uint32_t e = tile_receiver(a.tile_pfx, t, lane);
+  uint32_t lo[3], hi[3], len[3], x[3];
+  recv_lists(a, e, n_ep, nic, lo, hi);
+  for (int r = 0; r < 3; ++r) len[r] = hi[r] - lo[r];
+  const uint32_t total = len[0] + len[1] + len[2];
+  const uint32_t k0 = (t - a.tile_pfx[e]) * P;   // < total
+  lists_cut(a.index, a.n, lo, len, k0, lane, x);
   if (lane == 0) {
     const uint32_t m = total - k0 < P ? total - k0 : P;
     s_h[H_M] = m;

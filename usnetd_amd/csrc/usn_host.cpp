@@ -3880,6 +3880,114 @@ int usn_deliver_info(usn_ctx *c, const usn_delivery *d, void *stream, usn_delive
   return out->flags & (USN_DV_OVERFLOW | USN_DV_LONG) ? USN_ERANGE : USN_OK;
 }
 
+/* ---- round delivery: one ring per endpoint for a poll round (usn_deliver_round.hip) */
+struct RDeliveryLayout {
+  DeliveryLayout d;
+  size_t seg_off;
+};
+/* usn_delivery's arrays in their order, seg_off between ep_off and the header */
+static bool rdelivery_layout(uint64_t cap, uint32_t slot, RDeliveryLayout &L) {
+  if (!delivery_layout(cap, slot, L.d)) return false;
+  size_t off = L.d.hdr;
+  L.seg_off = off; off = align256(off + ((size_t)USN_ROUND_MAX * USN_DT_IDS + 1) * 4);
+  L.d.hdr = off; off = align256(off + usn::DELIVER_SCRATCH_OFF + usn::DELIVER_SCRATCH_BYTES);
+  L.d.total = off;
+  return true;
+}
+
+size_t usn_rdelivery_bytes(uint64_t cap_slots, uint32_t slot) {
+  RDeliveryLayout L;
+  return rdelivery_layout(cap_slots, slot, L) ? L.d.total : 0;
+}
+
+int usn_rdelivery_bind(void *mem, size_t bytes, uint64_t cap_slots, uint32_t slot, usn_rdelivery *out) {
+  RDeliveryLayout L;
+  if (!mem || !out || ((uintptr_t)mem & 15) != 0 || !rdelivery_layout(cap_slots, slot, L)) return USN_EINVAL;
+  if (bytes < L.d.total) return USN_ERANGE;
+  uint8_t *b = static_cast<uint8_t *>(mem);
+  out->frames = b + L.d.frames;
+  out->lens = reinterpret_cast<uint16_t *>(b + L.d.lens);
+  out->src = reinterpret_cast<uint32_t *>(b + L.d.src);
+  out->ep_off = reinterpret_cast<uint32_t *>(b + L.d.ep_off);
+  out->seg_off = reinterpret_cast<uint32_t *>(b + L.seg_off);
+  out->hdr = reinterpret_cast<usn_delivery_hdr *>(b + L.d.hdr);
+  out->cap = cap_slots;
+  out->slot = slot;
+  out->_r = 0;
+  return USN_OK;
+}
+
+int usn_deliver_round(usn_ctx *c, const usn_batch *b, const usn_result *r, uint32_t count,
+                      usn_rdelivery *d, void *stream) {
+  if (!c || !b || !r || !d || count == 0 || count > USN_ROUND_MAX) return USN_EINVAL;
+  if (!d->frames || !d->lens || !d->src || !d->ep_off || !d->seg_off || !d->hdr) return USN_EINVAL;
+  if (d->slot == 0 || d->slot % 16 != 0 || d->cap == 0 || d->cap > 0xFFFFFFFFull) return USN_EINVAL;
+  if ((((uintptr_t)d->frames | (uintptr_t)d->seg_off) & 15) != 0) return USN_EINVAL;
+  for (uint32_t k = 0; k < count; ++k)
+    if (!deliver_inputs_ok(&b[k], &r[k]) || (b[k].stride && d->slot < b[k].stride)) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  std::lock_guard<std::mutex> g(c->mu);
+  /* every ring is checked before the stream is touched */
+  uint32_t rep = 0;
+  for (uint32_t k = 0; k < count; ++k) {
+    for (const usn_ctx::Tx &t : c->txq)
+      if (t.decisions == r[k].decisions) return USN_EBUSY;   // lists not final before its usn_finalize
+    const auto br = c->batch_rep.find(r[k].decisions);
+    if (br == c->batch_rep.end()) return USN_EINVAL;         // nothing was classified into r[k]
+    if (k && br->second.rep != rep) return USN_EINVAL;       // one round, one replica
+    rep = br->second.rep;
+  }
+  Replica &R = c->reps[rep];
+  { int s = upload_eptab(c, R); if (s) return s; }
+  HIPCHK(hipSetDevice(R.device));
+  usn::RoundDeliverArgs a;
+  std::memset(&a, 0, sizeof a);
+  for (uint32_t k = 0; k < count; ++k) {
+    const auto le = c->lists_ev.find(r[k].decisions);        // lists built on the side stream
+    if (le != c->lists_ev.end() && le->second.ev)
+      HIPCHK(hipStreamWaitEvent((hipStream_t)stream, le->second.ev, 0));
+    a.frames[k] = b[k].frames;
+    a.stride[k] = b[k].stride;
+    a.offsets[k] = b[k].offsets;
+    a.lens[k] = b[k].lens;
+    a.index[k] = r[k].index;
+    a.bin_off[k] = r[k].bin_off;
+    a.summary[k] = r[k].summary;
+    a.n[k] = (uint32_t)b[k].n;
+    a.src[k] = b[k].src_endpoint;
+  }
+  for (uint32_t k = count; k < USN_ROUND_MAX; ++k) {   // ring 0 again, without frames
+    a.frames[k] = a.frames[0];
+    a.lens[k] = a.lens[0];
+    a.index[k] = a.index[0];
+    a.bin_off[k] = a.bin_off[0];
+    a.summary[k] = a.summary[0];
+    a.src[k] = a.src[0];
+  }
+  a.eptab = R.d_eptab;
+  a.out_frames = d->frames;
+  a.out_lens = d->lens;
+  a.out_src = d->src;
+  a.ep_off = d->ep_off;
+  a.seg_off = d->seg_off;
+  a.hdr = d->hdr;
+  a.tile_pfx = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(d->hdr) + usn::DELIVER_SCRATCH_OFF);
+  a.cap = (uint32_t)d->cap;
+  a.slot = d->slot;
+  // usn_deliver's pack grid: what the device holds at once
+  HIPCHK(usn::launch_deliver_round(a, (uint32_t)std::max(R.n_cu, 1) * 8u, (hipStream_t)stream));
+  if (c->sel < c->reps.size() && c->reps[c->sel].device != R.device) HIPCHK(hipSetDevice(c->device));
+  return USN_OK;
+}
+
+int usn_deliver_round_info(usn_ctx *c, const usn_rdelivery *d, void *stream, usn_delivery_hdr *out) {
+  if (!c || !d || !d->hdr || !out) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  HIPCHK(hipMemcpy(out, d->hdr, sizeof *out, hipMemcpyDeviceToHost));
+  return out->flags & (USN_DV_OVERFLOW | USN_DV_LONG) ? USN_ERANGE : USN_OK;
+}
+
 /* ---- packed delivery: byte-compact rings (usn_deliver_packed.hip) ----------- */
 struct PDeliveryLayout {
   size_t frames, off16, lens, src, ep_off, ep_boff, hdr, total;

@@ -324,6 +324,42 @@ constexpr size_t pdeliver_scratch_bytes(uint64_t cap) {
 }
 hipError_t launch_deliver_packed(const PackedDeliverArgs &a, uint32_t grid, hipStream_t stream);
 
+/* ---- round delivery (usn_deliver_round.hip): one ring per endpoint for the
+ * up to USN_ROUND_MAX rings of a poll round.  Two launches, whatever count is:
+ *   rdeliver_plan_kernel  one workgroup: per (endpoint id, ring) the slots of
+ *                         that segment, summed id-major / ring-minor (seg_off,
+ *                         ep_off), the header, and the tile prefix over the
+ *                         receivers' ROUND rings
+ *   rdeliver_pack_kernel  device-sized grid; a tile is USN_DELIVER_TILE slots
+ *                         of one receiver's round ring and may span segments:
+ *                         per intersected segment the three-list cut at the
+ *                         segment-local position, all their runs merged in LDS
+ *                         with the ring of every slot, then one gather
+ * The per-ring fields are arrays of USN_ROUND_MAX; entries from count on
+ * repeat ring 0 with n = 0, so the kernels treat all eight alike (no branch on
+ * count) and every position they clamp to n gives an empty list. */
+struct RoundDeliverArgs {
+  const uint8_t *frames[USN_ROUND_MAX];
+  uint64_t stride[USN_ROUND_MAX];
+  const uint64_t *offsets[USN_ROUND_MAX];
+  const uint16_t *lens[USN_ROUND_MAX];
+  const uint32_t *index[USN_ROUND_MAX];
+  const uint32_t *bin_off[USN_ROUND_MAX];
+  const usn_summary *summary[USN_ROUND_MAX];
+  uint32_t n[USN_ROUND_MAX];     /* frames in ring k (< 2^32 - 1) */
+  uint32_t src[USN_ROUND_MAX];   /* ring k's source endpoint */
+  const uint16_t *eptab;    /* as DeliverArgs */
+  uint8_t *out_frames;
+  uint16_t *out_lens;
+  uint32_t *out_src;
+  uint32_t *ep_off;         /* [USN_DT_IDS] */
+  uint32_t *seg_off;        /* [USN_ROUND_MAX * USN_DT_IDS + 1] */
+  usn_delivery_hdr *hdr;
+  uint32_t *tile_pfx;       /* [USN_DT_IDS], as DeliverArgs, over the round rings */
+  uint32_t cap, slot;
+};
+hipError_t launch_deliver_round(const RoundDeliverArgs &a, uint32_t pack_grid, hipStream_t stream);
+
 }  // namespace usn
 
 /* the same kernels at 512 threads per tile (a second compilation of

@@ -23,6 +23,7 @@ USN_WINDOW = 64
 USN_WINDOW_MAX = 80
 USN_MAX_ENDPOINTS = 4095
 USN_MAX_BINS = USN_MAX_ENDPOINTS + 3
+USN_ROUND_MAX = 8        # rings of one usn_deliver_round
 USN_DELIVER_TILE = 512   # output slots per pack tile of usn_deliver (usn_classify.h)
 DV_OVERFLOW, DV_LONG = 1, 2
 DV_OVERFLOW_BYTES = 4   # usn_deliver_packed: need_bytes > cap_bytes
@@ -84,6 +85,12 @@ class Delivery(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("lens", C.c_void_p), ("src", C.c_void_p),
                 ("ep_off", C.c_void_p), ("hdr", C.c_void_p), ("cap", C.c_uint64),
                 ("slot", C.c_uint32), ("_r", C.c_uint32)]
+
+
+class RDelivery(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("lens", C.c_void_p), ("src", C.c_void_p),
+                ("ep_off", C.c_void_p), ("seg_off", C.c_void_p), ("hdr", C.c_void_p),
+                ("cap", C.c_uint64), ("slot", C.c_uint32), ("_r", C.c_uint32)]
 
 
 class PDeliveryHdr(C.Structure):
@@ -167,12 +174,18 @@ def load(path: str | None = None):
         "usn_pdelivery_bind": ([P, SZ, U64, U64, C.POINTER(PDelivery)], I),
         "usn_deliver_packed": ([P, C.POINTER(Batch), C.POINTER(Result), C.POINTER(PDelivery), P], I),
         "usn_deliver_packed_info": ([P, C.POINTER(PDelivery), P, C.POINTER(PDeliveryHdr)], I),
+        "usn_rdelivery_bytes": ([U64, U32], SZ),
+        "usn_rdelivery_bind": ([P, SZ, U64, U32, C.POINTER(RDelivery)], I),
+        "usn_deliver_round": ([P, P, P, U32, C.POINTER(RDelivery), P], I),
+        "usn_deliver_round_info": ([P, C.POINTER(RDelivery), P, C.POINTER(DeliveryHdr)], I),
     }
     optional = {"usn_set_frame_reader", "usn_ctx_create_group", "usn_ctx_replicas",
                 "usn_replica_select", "usn_replica_device", "usn_result_bytes_ep",
                 "usn_set_lists_async", "usn_lists_wait", "usn_result_release", "usn_delivery_bytes",
                 "usn_delivery_bind", "usn_deliver", "usn_deliver_info", "usn_pdelivery_bytes",
-                "usn_pdelivery_bind", "usn_deliver_packed", "usn_deliver_packed_info"}   # A/B builds of older ABI versions lack these
+                "usn_pdelivery_bind", "usn_deliver_packed", "usn_deliver_packed_info",
+                "usn_rdelivery_bytes", "usn_rdelivery_bind", "usn_deliver_round",
+                "usn_deliver_round_info"}   # A/B builds of older ABI versions lack these
     for name, (args, res) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -196,7 +209,8 @@ EXPORTED = ["usn_abi_version", "usn_strerror", "usn_last_hip_error", "usn_ctx_cr
             "usn_ctx_replicas", "usn_replica_select", "usn_replica_device", "usn_set_lists_async",
             "usn_lists_wait", "usn_result_release", "usn_delivery_bytes", "usn_delivery_bind",
             "usn_deliver", "usn_deliver_info", "usn_pdelivery_bytes", "usn_pdelivery_bind",
-            "usn_deliver_packed", "usn_deliver_packed_info"]
+            "usn_deliver_packed", "usn_deliver_packed_info", "usn_rdelivery_bytes",
+            "usn_rdelivery_bind", "usn_deliver_round", "usn_deliver_round_info"]
 
 
 def check(rc, what=""):
@@ -461,6 +475,16 @@ class Ctx:
         check(self.L.usn_deliver_packed(self.h, C.byref(batch.desc), C.byref(result.desc),
                                         C.byref(delivery.desc), stream), "usn_deliver_packed")
 
+    def deliver_round(self, batches, results, delivery: "DeviceRoundDelivery", stream=None):
+        """One ring per endpoint for a whole poll round (usn_deliver_round): the
+        up to USN_ROUND_MAX rings in poll order, every result final; endpoint e's
+        ring is its usn_deliver segments of ring 0, 1, ... back to back."""
+        n = len(batches)
+        ba = (Batch * n)(*[b.desc for b in batches])
+        ra = (Result * n)(*[r.desc for r in results])
+        check(self.L.usn_deliver_round(self.h, C.cast(ba, C.c_void_p), C.cast(ra, C.c_void_p), n,
+                                       C.byref(delivery.desc), stream), "usn_deliver_round")
+
 
 class DeviceBatch:
     """Frames + lengths resident in HBM (one drained rx ring)."""
@@ -642,6 +666,47 @@ class DeviceDelivery:
         if self.buf is not None:
             self.buf.free()
             self.buf = None
+
+
+class DeviceRoundDelivery(DeviceDelivery):
+    """One usn_rdelivery: DeviceDelivery's arrays for a poll round, plus seg_off:
+    segment (e, k), ring k's frames for endpoint e, is slots
+    [seg_off[8e + k], seg_off[8e + k + 1])."""
+
+    def __init__(self, ctx: Ctx, cap_slots: int, slot: int, poison: int | None = None):
+        self.ctx = ctx
+        self.cap = int(cap_slots)
+        self.slot = int(slot)
+        nbytes = ctx.L.usn_rdelivery_bytes(self.cap, self.slot)
+        if nbytes == 0:
+            raise UsnError("usn_rdelivery_bytes: bad capacity %d or slot %d" % (self.cap, self.slot))
+        self.buf = ctx.alloc(nbytes)
+        self.desc = RDelivery()
+        check(ctx.L.usn_rdelivery_bind(self.buf.ptr, nbytes, self.cap, self.slot, C.byref(self.desc)),
+              "usn_rdelivery_bind")
+        if poison is not None:
+            check(ctx.L.usn_memset_d(ctx.h, self.buf.ptr, poison, nbytes, None), "usn_memset_d")
+            ctx.sync()
+
+    def info(self, stream=None, strict=True) -> DeliveryHdr:
+        h = DeliveryHdr()
+        rc = self.ctx.L.usn_deliver_round_info(self.ctx.h, C.byref(self.desc), stream, C.byref(h))
+        if strict or rc != USN_ERANGE:
+            check(rc, "usn_deliver_round_info")
+        h.status = rc
+        return h
+
+    def seg_off(self) -> np.ndarray:
+        """all USN_ROUND_MAX * (USN_MAX_ENDPOINTS + 1) + 1 segment offsets"""
+        return self._get(self.desc.seg_off, np.uint32, USN_ROUND_MAX * (USN_MAX_ENDPOINTS + 1) + 1)
+
+    def ring(self, e: int):
+        """(src_idx, lens, bytes[k, slot], ring ids) of endpoint e's round ring;
+        src_idx counts inside the slot's own ring"""
+        so = self.seg_off()[USN_ROUND_MAX * e:USN_ROUND_MAX * (e + 1) + 1].astype(np.int64)
+        k0, k1 = int(so[0]), int(so[-1])
+        rings = np.repeat(np.arange(USN_ROUND_MAX, dtype=np.uint8), np.diff(so))
+        return self.src(k0, k1), self.lens(k0, k1), self.slots(k0, k1), rings
 
 
 class DevicePackedDelivery:
