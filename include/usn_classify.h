@@ -565,6 +565,89 @@ int usn_deliver_round(usn_ctx *ctx, const usn_batch *b, const usn_result *r, uin
 int usn_deliver_round_info(usn_ctx *ctx, const usn_rdelivery *d, void *hip_stream,
                            usn_delivery_hdr *host_out);
 
+/* ---- ring delivery: a poll round appended to persistent endpoint rings -------
+ * The modes above write a fresh, exactly sized region per call.  An endpoint of
+ * the reference owns ONE ring of fixed size: a write into a full ring fails
+ * and that frame alone is lost (endpoint.rs:75-82).  A ring set is that: one
+ * circular ring of `slot`-byte slots per endpoint id in device memory, with
+ * free-running 32-bit head / tail counters, and usn_deliver_rings appends a
+ * poll round to it.  Nothing is sized per call, nothing overflows globally,
+ * and a consumer needs only tail[e].
+ *
+ * For receiver e with S = ring_off[e+1] - ring_off[e] slots (0 or a power of
+ * two): segment (e, k) is offered exactly what usn_deliver_round defines (the
+ * receiver rule, the order, registered ids only).  fill = tail[e] - head[e]
+ * in 32-bit arithmetic and free = S - min(fill, S): a head "ahead of" the
+ * tail, a fill above S and S = 0 all give free = 0.  The first min(offered,
+ * free) frames of e's round ring, in round order, are accepted, the rest are
+ * dropped (nothing is consumed within a call): seg_acc[8e + k] is segment k's
+ * accepted share, acc[e] their sum, drop[e] the rest (saturating), first[e]
+ * the tail before the call.  Accepted frame j lands in slot ring_off[e] +
+ * ((first[e] + j) & (S - 1)); lens[], src[] and the slot bytes follow
+ * usn_deliver (bytes [0, len) the frame, [len, ceil16(len)) zero, truncated
+ * at `slot` with USN_DV_LONG, which only an ACCEPTED frame sets).  No other
+ * slot is touched, slots between head and tail are never overwritten, and a
+ * dropped frame's bytes and list entries are never read.
+ *
+ * tail[e] becomes first[e] + acc[e] in the call's last launch only, after
+ * every slot of the call is written: a reader ordered behind the call (stream
+ * or event) sees complete slots below tail.  Calls on one ring set must be
+ * stream-ordered with each other and with head updates. */
+#define USN_HAS_DELIVER_RINGS 1
+#define USN_DV_DROPPED 8u   /* at least one offered frame found its ring full */
+typedef struct {
+  uint64_t offered;     /* frames the round's rule gives all receivers (usn_deliver_round's need, unsaturated) */
+  uint64_t dropped;     /* offered - accepted */
+  uint32_t accepted;    /* slots written by this call */
+  uint32_t n_recv;      /* receivers with accepted > 0 */
+  uint32_t flags;       /* USN_DV_LONG (an ACCEPTED frame longer than slot), USN_DV_DROPPED */
+  uint32_t _r;
+} usn_ringset_hdr;
+typedef struct {
+  uint8_t  *frames;     /* total * slot bytes */
+  uint16_t *lens;       /* total */
+  uint32_t *src;        /* total: frame index inside the slot's own source ring */
+  uint32_t *ring_off;   /* USN_MAX_ENDPOINTS + 2: ring of id e = slots [ring_off[e], ring_off[e+1]) */
+  uint32_t *head;       /* USN_MAX_ENDPOINTS + 1, free-running, written by the consumer only */
+  uint32_t *tail;       /* USN_MAX_ENDPOINTS + 1, free-running, written by the commit launch only */
+  uint32_t *first;      /* per id: tail[e] before this call */
+  uint32_t *acc;        /* per id: frames accepted by this call */
+  uint32_t *drop;       /* per id: frames dropped by this call (saturating) */
+  uint32_t *seg_acc;    /* USN_ROUND_MAX * (USN_MAX_ENDPOINTS + 1): accepted frames of segment (e, k) at [8e + k] */
+  usn_ringset_hdr *hdr; /* followed by the kernels' scratch (tile prefix, next tails) */
+  uint64_t total;
+  uint32_t slot, ready; /* ready: set by usn_ringset_init */
+} usn_ringset;
+/* Bytes of a ring set of total_slots slots of `slot` bytes: 0 unless slot is a
+ * non-zero multiple of 16 and total_slots lies in [1, 2^32).  usn_ringset_bind
+ * carves device (or, for layout checks, host) memory of that size into
+ * 256-byte aligned arrays and clears `ready`: USN_EINVAL for such arguments,
+ * USN_ERANGE when `bytes` is too small.  Both only carve memory. */
+size_t usn_ringset_bytes(uint64_t total_slots, uint32_t slot);
+int usn_ringset_bind(void *dev_mem, size_t bytes, uint64_t total_slots, uint32_t slot, usn_ringset *out);
+/* Lays the rings out back to back: ring_slots[e], e < n_ids <=
+ * USN_MAX_ENDPOINTS, is 0 or a power of two of at most 2^30, ids from n_ids on
+ * get 0, and the sum must not exceed total (else USN_EINVAL).  Uploads
+ * ring_off, zeroes head, tail, the per-call arrays and the header, and sets
+ * `ready`.  A setup call: it synchronises `hip_stream`. */
+int usn_ringset_init(usn_ctx *ctx, usn_ringset *rs, const uint32_t *ring_slots, uint32_t n_ids,
+                     void *hip_stream);
+/* Copies absolute head counters for ids below n_ids on `hip_stream` and returns
+ * when the caller's array may be reused.  `head` is ordinary device memory: a
+ * consumer may write it by any other means ordered with the calls. */
+int usn_ringset_set_head(usn_ctx *ctx, usn_ringset *rs, const uint32_t *head, uint32_t n_ids,
+                         void *hip_stream);
+/* usn_deliver_round's arguments, validation (the slot rules against rs->slot),
+ * event waits, receiver table and return codes, plus USN_EINVAL for a ring set
+ * that is not ready.  Three launches on `hip_stream` whatever count is (plan,
+ * pack, commit); no host synchronisation and no copy in the steady state. */
+int usn_deliver_rings(usn_ctx *ctx, const usn_batch *b, const usn_result *r, uint32_t count,
+                      usn_ringset *rs, void *hip_stream);
+/* Synchronises `hip_stream` and copies the header to the host: USN_ERANGE
+ * when either flag is set (host_out is filled all the same). */
+int usn_deliver_rings_info(usn_ctx *ctx, const usn_ringset *rs, void *hip_stream,
+                           usn_ringset_hdr *host_out);
+
 /* Forget the carried decision cache of one endpoint (last_pkt = None). */
 int usn_cache_clear(usn_ctx *ctx, uint16_t endpoint);
 

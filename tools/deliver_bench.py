@@ -19,8 +19,15 @@ per endpoint, two launches) next to the loop of --multi usn_deliver calls on
 the same rings and results, and to ONE device-to-device copy of the same
 need x slot bytes, the three alternating in blocks.
 
+--rings times usn_deliver_rings (the round appended to persistent endpoint
+rings: three launches) next to usn_deliver_round on the same rings and results
+and to ONE device-to-device copy of the accepted bytes, alternating in blocks:
+once with rings ample enough that nothing drops, once with rings of about half
+of what each endpoint is offered.  Heads are reset to the tails between calls
+(a device copy outside the timed span), so the rings never fill up.
+
 usage: python tools/deliver_bench.py [--config c5] [--frames N] [--multi 2] [--rounds 2]
-                                     [--launches 120] [--slot 64] [--packed | --round]
+                                     [--launches 120] [--slot 64] [--packed | --round | --rings]
                                      [--json out.json]
 """
 import argparse
@@ -47,6 +54,7 @@ def main():
     ap.add_argument("--slot", type=int, default=64)
     ap.add_argument("--packed", action="store_true")
     ap.add_argument("--round", action="store_true")
+    ap.add_argument("--rings", action="store_true")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     n, Q, R = a.frames, a.multi, a.rounds
@@ -131,6 +139,8 @@ def main():
                       timed, block)
     if a.round:
         return round_mode(a, ctx, s, hip, bs, rs, dvs, need, deliver, timed, block)
+    if a.rings:
+        return rings_mode(a, ctx, s, hip, bs, rs, need, timed, block)
     dl_us, cp_us = [], []
     while len(dl_us) < a.launches:
         dl_us += timed(deliver, block)
@@ -195,6 +205,84 @@ def round_mode(a, ctx, s, hip, bs, rs, dvs, need, deliver, timed, block):
     out["round_over_loop"] = round(out["round_us"] / out["deliver_loop_us"], 3)
     out["round_over_copy"] = round(out["round_us"] / out["d2d_copy_us"], 2)
     out["loop_over_copy"] = round(out["deliver_loop_us"] / out["d2d_copy_us"], 2)
+    print(json.dumps(out), flush=True)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+    ctx.close()
+
+
+def rings_mode(a, ctx, s, hip, bs, rs, need, timed, block):
+    """usn_deliver_rings (ample rings, then rings that drop about half) against usn_deliver_round
+    and one copy of the accepted bytes"""
+    n, Q, R = a.frames, a.multi, a.rounds
+    rds = [lib.DeviceRoundDelivery(ctx, n * Q, a.slot) for _ in range(R)]
+    ctx.deliver_round(bs[0], rs[0], rds[0], s)
+    assert rds[0].info(s).need == need
+    cnt = np.diff(rds[0].ep_off().astype(np.int64), append=need)   # what a call offers each endpoint
+    ids = int(np.flatnonzero(cnt)[-1]) + 1
+    pow2 = lambda v: np.where(v > 0, 2 ** np.ceil(np.log2(np.maximum(v, 1))), 0).astype(np.uint32)
+    ample = pow2(cnt[:ids])
+    half = pow2(np.where(cnt[:ids] > 0, np.maximum(cnt[:ids] / 2 ** 1.5, 1), 0))   # the power of two nearest cnt / 2
+    sets = {"rings": [lib.DeviceRingSet(ctx, ample, a.slot) for _ in range(R)],
+            "rings_half": [lib.DeviceRingSet(ctx, half, a.slot) for _ in range(R)]}
+    cp_src = ctx.alloc(need * a.slot)
+    hdrs = {}
+
+    def deliver_round(r):
+        ctx.deliver_round(bs[r], rs[r], rds[r], s)
+
+    def copy(r, slots=need):
+        assert hip.hipMemcpyDtoDAsync(rds[r].desc.frames, cp_src.ptr, slots * a.slot, s) == 0
+
+    def rings(name):
+        return lambda r: ctx.deliver_rings(bs[r], rs[r], sets[name][r], s)
+
+    def drain(name):   # head = tail on the stream, outside the timed span
+        def f(r):
+            d = sets[name][r].desc
+            assert hip.hipMemcpyDtoDAsync(d.head, d.tail, 4 * (lib.USN_MAX_ENDPOINTS + 1), s) == 0
+        return f
+
+    # the first append (heads 0) against the round delivery: two endpoints' rings
+    for name in sets:
+        rings(name)(0)
+        hdrs[name] = sets[name][0].info(s, strict=False)
+    assert (hdrs["rings"].accepted, hdrs["rings"].flags) == (need, 0), "the ample rings dropped or truncated"
+    for e in (2, ids - 1):
+        src, lens, slots, _ = rds[0].ring(e)
+        for name, rsz in (("rings", ample), ("rings_half", half)):
+            k = min(int(rsz[e]), lens.size)
+            for got, want in zip(sets[name][0].ring(e), (lens, src, slots)):
+                assert np.array_equal(got, want[:k]), "ring %d differs from the round delivery's" % e
+    acc_half = int(hdrs["rings_half"].accepted)
+    for name in sets:
+        for r in list(range(R)) * 2:   # warm-up
+            drain(name)(r)
+            rings(name)(r)
+        for r in range(R):
+            drain(name)(r)
+    us = {k: [] for k in ("rings", "round", "d2d_copy", "rings_half", "d2d_copy_half")}
+    while len(us["rings"]) < a.launches:
+        us["rings"] += timed(rings("rings"), block, after=drain("rings"))
+        us["round"] += timed(deliver_round, block)
+        us["d2d_copy"] += timed(copy, block)
+        us["rings_half"] += timed(rings("rings_half"), block, after=drain("rings_half"))
+        us["d2d_copy_half"] += timed(lambda r: copy(r, acc_half), block)
+    for r in range(R):   # the last timed calls: nothing dropped from the ample rings, the same share from the others
+        assert sets["rings"][r].info(s).accepted == need
+        assert sets["rings_half"][r].info(s, strict=False).accepted == acc_half
+    out = dict(config=a.config, frames_per_call=n * Q, rings=Q, slot=a.slot, offered_slots=need,
+               endpoints_with_a_ring=int((ample > 0).sum()), ring_slots_ample=int(ample.sum()),
+               ring_slots_half=int(half.sum()), accepted_half=acc_half,
+               dropped_share_half=round(1 - acc_half / max(need, 1), 3), launches=len(us["rings"]),
+               launches_per_call_rings=3, launches_per_call_round=2)
+    for k, v in us.items():
+        out.update(stats(v, k))
+    out["rings_over_round"] = round(out["rings_us"] / out["round_us"], 3)
+    out["rings_over_copy"] = round(out["rings_us"] / out["d2d_copy_us"], 2)
+    out["rings_half_over_rings"] = round(out["rings_half_us"] / out["rings_us"], 3)
+    out["rings_half_over_copy"] = round(out["rings_half_us"] / out["d2d_copy_half_us"], 2)
     print(json.dumps(out), flush=True)
     if a.json:
         with open(a.json, "w") as fh:

@@ -4,7 +4,8 @@
  * round's rings in one): the receiver rule, the plan over the 4096 endpoint
  * ids, a tile's receiver, the three-list cut and the rank merge in LDS.  Device
  * code only; A is DeliverArgs or PackedDeliverArgs (the fields used here have
- * the same names in both) or, for recv_lists, one ring of a round.
+ * the same names in both) or, for recv_lists, one ring of a round
+ * (usn_deliver_rings.hip appends such a round to persistent rings).
  */
 #ifndef USN_DELIVER_COMMON_H
 #define USN_DELIVER_COMMON_H
@@ -245,6 +246,27 @@ __device__ __forceinline__ void tile_merge(const A &a, const uint32_t *s_h, uint
     }
   }
 }
+
+/* ---- what the modes over a poll round's rings share (usn_deliver_round.hip,
+ * usn_deliver_rings.hip) */
+#define USN_GLOBAL __attribute__((address_space(1)))
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+template <class T>
+__device__ __forceinline__ const USN_GLOBAL T *as_global(const T *p) { return (const USN_GLOBAL T *)p; }
+
+/* recv_lists' view of one ring */
+struct RingLists {
+  const uint16_t *eptab;
+  const uint32_t *bin_off;
+  uint32_t src, n;
+};
+
+__device__ __forceinline__ uint32_t sat32(unsigned long long v) {
+  return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v;
+}
+
+/* what wave 0 hands the workgroup per intersected segment */
+enum { S_RING = 0, S_DST = 1, S_CNT = 2, S_CUT = 3, S_RL = 6, S_WORDS = 9 };
 
 }  // namespace dv
 }  // namespace usn

@@ -48,22 +48,6 @@ constexpr uint32_t UNR = 4;                  // frames a lane group has in fligh
 constexpr uint32_t RM = USN_ROUND_MAX;
 static_assert(RM == 8 && RM + 1 <= 64, "a receiver's segment offsets: one lane each, 8e + k");
 
-#define USN_GLOBAL __attribute__((address_space(1)))
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-template <class T>
-__device__ __forceinline__ const USN_GLOBAL T *as_global(const T *p) { return (const USN_GLOBAL T *)p; }
-
-/* recv_lists' view of one ring */
-struct RingLists {
-  const uint16_t *eptab;
-  const uint32_t *bin_off;
-  uint32_t src, n;
-};
-
-__device__ __forceinline__ uint32_t sat32(unsigned long long v) {
-  return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v;
-}
-
 __global__ __launch_bounds__(PLAN_T) void rdeliver_plan_kernel(RoundDeliverArgs a) {
   __shared__ unsigned long long wsum[PLAN_T / 64];
   __shared__ uint32_t s_recv;
@@ -161,9 +145,6 @@ __global__ __launch_bounds__(PLAN_T) void rdeliver_plan_kernel(RoundDeliverArgs 
     a.hdr->n_recv = s_recv;
   }
 }
-
-/* what wave 0 hands the workgroup per intersected segment */
-enum { S_RING = 0, S_DST = 1, S_CNT = 2, S_CUT = 3, S_RL = 6, S_WORDS = 9 };
 
 __global__ __launch_bounds__(PACK_T) void rdeliver_pack_kernel(RoundDeliverArgs a) {
   __shared__ uint32_t s_run[3][P];

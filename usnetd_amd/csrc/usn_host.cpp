@@ -3917,17 +3917,16 @@ int usn_rdelivery_bind(void *mem, size_t bytes, uint64_t cap_slots, uint32_t slo
   return USN_OK;
 }
 
-int usn_deliver_round(usn_ctx *c, const usn_batch *b, const usn_result *r, uint32_t count,
-                      usn_rdelivery *d, void *stream) {
-  if (!c || !b || !r || !d || count == 0 || count > USN_ROUND_MAX) return USN_EINVAL;
-  if (!d->frames || !d->lens || !d->src || !d->ep_off || !d->seg_off || !d->hdr) return USN_EINVAL;
-  if (d->slot == 0 || d->slot % 16 != 0 || d->cap == 0 || d->cap > 0xFFFFFFFFull) return USN_EINVAL;
-  if ((((uintptr_t)d->frames | (uintptr_t)d->seg_off) & 15) != 0) return USN_EINVAL;
-  for (uint32_t k = 0; k < count; ++k)
-    if (!deliver_inputs_ok(&b[k], &r[k]) || (b[k].stride && d->slot < b[k].stride)) return USN_EINVAL;
-  if (c->reps.empty()) return USN_ENODEV;
-  std::lock_guard<std::mutex> g(c->mu);
-  /* every ring is checked before the stream is touched */
+/* With c->mu held, for the rings of a poll round (usn_deliver_round,
+ * usn_deliver_rings): every ring is checked before the stream is touched; then
+ * the one replica that classified them (*Rp) with its receiver table at today's
+ * endpoint set, `stream` ordered after every result's lists, and the per-ring
+ * fields of the kernel argument A (entries from count on: ring 0 again,
+ * without frames) */
+extern "C++" {
+template <class A>
+static int round_rings(usn_ctx *c, const usn_batch *b, const usn_result *r, uint32_t count, void *stream,
+                       Replica **Rp, A &a) {
   uint32_t rep = 0;
   for (uint32_t k = 0; k < count; ++k) {
     for (const usn_ctx::Tx &t : c->txq)
@@ -3940,8 +3939,6 @@ int usn_deliver_round(usn_ctx *c, const usn_batch *b, const usn_result *r, uint3
   Replica &R = c->reps[rep];
   { int s = upload_eptab(c, R); if (s) return s; }
   HIPCHK(hipSetDevice(R.device));
-  usn::RoundDeliverArgs a;
-  std::memset(&a, 0, sizeof a);
   for (uint32_t k = 0; k < count; ++k) {
     const auto le = c->lists_ev.find(r[k].decisions);        // lists built on the side stream
     if (le != c->lists_ev.end() && le->second.ev)
@@ -3965,6 +3962,26 @@ int usn_deliver_round(usn_ctx *c, const usn_batch *b, const usn_result *r, uint3
     a.src[k] = a.src[0];
   }
   a.eptab = R.d_eptab;
+  *Rp = &R;
+  return USN_OK;
+}
+}  // extern "C++"
+
+int usn_deliver_round(usn_ctx *c, const usn_batch *b, const usn_result *r, uint32_t count,
+                      usn_rdelivery *d, void *stream) {
+  if (!c || !b || !r || !d || count == 0 || count > USN_ROUND_MAX) return USN_EINVAL;
+  if (!d->frames || !d->lens || !d->src || !d->ep_off || !d->seg_off || !d->hdr) return USN_EINVAL;
+  if (d->slot == 0 || d->slot % 16 != 0 || d->cap == 0 || d->cap > 0xFFFFFFFFull) return USN_EINVAL;
+  if ((((uintptr_t)d->frames | (uintptr_t)d->seg_off) & 15) != 0) return USN_EINVAL;
+  for (uint32_t k = 0; k < count; ++k)
+    if (!deliver_inputs_ok(&b[k], &r[k]) || (b[k].stride && d->slot < b[k].stride)) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  std::lock_guard<std::mutex> g(c->mu);
+  usn::RoundDeliverArgs a;
+  std::memset(&a, 0, sizeof a);
+  Replica *Rp = nullptr;
+  { int s = round_rings(c, b, r, count, stream, &Rp, a); if (s) return s; }
+  Replica &R = *Rp;
   a.out_frames = d->frames;
   a.out_lens = d->lens;
   a.out_src = d->src;
@@ -3986,6 +4003,148 @@ int usn_deliver_round_info(usn_ctx *c, const usn_rdelivery *d, void *stream, usn
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   HIPCHK(hipMemcpy(out, d->hdr, sizeof *out, hipMemcpyDeviceToHost));
   return out->flags & (USN_DV_OVERFLOW | USN_DV_LONG) ? USN_ERANGE : USN_OK;
+}
+
+/* ---- ring delivery: a poll round appended to persistent rings (usn_deliver_rings.hip) */
+struct RingSetLayout {
+  size_t frames, lens, src, ring_off, head, tail, first, acc, drop, seg_acc, hdr, total;
+};
+static bool ringset_layout(uint64_t slots, uint32_t slot, RingSetLayout &L) {
+  if (slot == 0 || slot % 16 != 0 || slots == 0 || slots > 0xFFFFFFFFull) return false;
+  const size_t ids = (size_t)USN_DT_IDS * 4;
+  size_t off = 0;
+  L.frames = off; off = align256(off + (size_t)slots * slot);
+  L.lens = off; off = align256(off + (size_t)slots * 2);
+  L.src = off; off = align256(off + (size_t)slots * 4);
+  L.ring_off = off; off = align256(off + ids + 4);
+  L.head = off; off = align256(off + ids);
+  L.tail = off; off = align256(off + ids);
+  L.first = off; off = align256(off + ids);
+  L.acc = off; off = align256(off + ids);
+  L.drop = off; off = align256(off + ids);
+  L.seg_acc = off; off = align256(off + ids * USN_ROUND_MAX);
+  L.hdr = off; off = align256(off + usn::DELIVER_SCRATCH_OFF + usn::RINGS_SCRATCH_BYTES);
+  L.total = off;
+  return true;
+}
+
+size_t usn_ringset_bytes(uint64_t total_slots, uint32_t slot) {
+  RingSetLayout L;
+  return ringset_layout(total_slots, slot, L) ? L.total : 0;
+}
+
+int usn_ringset_bind(void *mem, size_t bytes, uint64_t total_slots, uint32_t slot, usn_ringset *out) {
+  RingSetLayout L;
+  if (!mem || !out || ((uintptr_t)mem & 15) != 0 || !ringset_layout(total_slots, slot, L)) return USN_EINVAL;
+  if (bytes < L.total) return USN_ERANGE;
+  uint8_t *b = static_cast<uint8_t *>(mem);
+  auto u32 = [b](size_t off) { return reinterpret_cast<uint32_t *>(b + off); };
+  out->frames = b + L.frames;
+  out->lens = reinterpret_cast<uint16_t *>(b + L.lens);
+  out->src = u32(L.src);
+  out->ring_off = u32(L.ring_off);
+  out->head = u32(L.head);
+  out->tail = u32(L.tail);
+  out->first = u32(L.first);
+  out->acc = u32(L.acc);
+  out->drop = u32(L.drop);
+  out->seg_acc = u32(L.seg_acc);
+  out->hdr = reinterpret_cast<usn_ringset_hdr *>(b + L.hdr);
+  out->total = total_slots;
+  out->slot = slot;
+  out->ready = 0;
+  return USN_OK;
+}
+
+/* what the ring entry points ask of a bound ring set */
+static bool ringset_ok(const usn_ringset *rs) {
+  if (!rs->frames || !rs->lens || !rs->src || !rs->ring_off || !rs->head || !rs->tail || !rs->first ||
+      !rs->acc || !rs->drop || !rs->seg_acc || !rs->hdr)
+    return false;
+  if (rs->slot == 0 || rs->slot % 16 != 0 || rs->total == 0 || rs->total > 0xFFFFFFFFull) return false;
+  const uintptr_t vec = (uintptr_t)rs->frames | (uintptr_t)rs->ring_off | (uintptr_t)rs->head |
+                        (uintptr_t)rs->tail | (uintptr_t)rs->first | (uintptr_t)rs->acc |
+                        (uintptr_t)rs->drop | (uintptr_t)rs->seg_acc | (uintptr_t)rs->hdr;
+  return (vec & 15) == 0;   // the kernels' 16-byte loads and stores
+}
+
+int usn_ringset_init(usn_ctx *c, usn_ringset *rs, const uint32_t *ring_slots, uint32_t n_ids, void *stream) {
+  if (!c || !rs || !ringset_ok(rs) || (!ring_slots && n_ids) || n_ids > USN_MAX_ENDPOINTS) return USN_EINVAL;
+  std::vector<uint32_t> off(USN_DT_IDS + 1, 0u);
+  uint64_t sum = 0;
+  for (uint32_t e = 0; e < USN_DT_IDS; ++e) {
+    const uint32_t S = e < n_ids ? ring_slots[e] : 0u;
+    if ((S & (S - 1)) != 0 || S > (1u << 30)) return USN_EINVAL;
+    off[e] = (uint32_t)sum;
+    sum += S;
+    if (sum > rs->total) return USN_EINVAL;
+  }
+  off[USN_DT_IDS] = (uint32_t)sum;
+  if (c->device < 0) return USN_ENODEV;
+  rs->ready = 0;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  /* head .. seg_acc and the header with its scratch lie behind ring_off in one piece */
+  uint8_t *zero = reinterpret_cast<uint8_t *>(rs->head);
+  const size_t zbytes = (size_t)(reinterpret_cast<uint8_t *>(rs->hdr) - zero) + usn::DELIVER_SCRATCH_OFF +
+                        usn::RINGS_SCRATCH_BYTES;
+  HIPCHK(hipMemsetAsync(zero, 0, zbytes, st));
+  HIPCHK(hipMemcpyAsync(rs->ring_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  rs->ready = 1;
+  return USN_OK;
+}
+
+int usn_ringset_set_head(usn_ctx *c, usn_ringset *rs, const uint32_t *head, uint32_t n_ids, void *stream) {
+  if (!c || !rs || !rs->head || !head || n_ids > USN_MAX_ENDPOINTS) return USN_EINVAL;
+  if (c->device < 0) return USN_ENODEV;
+  if (!rs->ready) return USN_EINVAL;
+  if (n_ids == 0) return USN_OK;
+  HIPCHK(hipMemcpyAsync(rs->head, head, (size_t)n_ids * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));   // the caller's array may be reused
+  return USN_OK;
+}
+
+int usn_deliver_rings(usn_ctx *c, const usn_batch *b, const usn_result *r, uint32_t count,
+                      usn_ringset *rs, void *stream) {
+  if (!c || !b || !r || !rs || count == 0 || count > USN_ROUND_MAX) return USN_EINVAL;
+  if (!ringset_ok(rs) || !rs->ready) return USN_EINVAL;
+  for (uint32_t k = 0; k < count; ++k)
+    if (!deliver_inputs_ok(&b[k], &r[k]) || (b[k].stride && rs->slot < b[k].stride)) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  std::lock_guard<std::mutex> g(c->mu);
+  usn::RingsDeliverArgs a;
+  std::memset(&a, 0, sizeof a);
+  Replica *Rp = nullptr;
+  { int s = round_rings(c, b, r, count, stream, &Rp, a); if (s) return s; }
+  Replica &R = *Rp;
+  a.out_frames = rs->frames;
+  a.out_lens = rs->lens;
+  a.out_src = rs->src;
+  a.ring_off = rs->ring_off;
+  a.head = rs->head;
+  a.tail = rs->tail;
+  a.first = rs->first;
+  a.acc = rs->acc;
+  a.drop = rs->drop;
+  a.seg_acc = rs->seg_acc;
+  a.hdr = rs->hdr;
+  a.tile_pfx = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(rs->hdr) + usn::DELIVER_SCRATCH_OFF);
+  a.next_tail = a.tile_pfx + USN_DT_IDS;
+  a.total = (uint32_t)rs->total;
+  a.slot = rs->slot;
+  // usn_deliver's pack grid: what the device holds at once
+  HIPCHK(usn::launch_deliver_rings(a, (uint32_t)std::max(R.n_cu, 1) * 8u, (hipStream_t)stream));
+  if (c->sel < c->reps.size() && c->reps[c->sel].device != R.device) HIPCHK(hipSetDevice(c->device));
+  return USN_OK;
+}
+
+int usn_deliver_rings_info(usn_ctx *c, const usn_ringset *rs, void *stream, usn_ringset_hdr *out) {
+  if (!c || !rs || !rs->hdr || !out) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  HIPCHK(hipMemcpy(out, rs->hdr, sizeof *out, hipMemcpyDeviceToHost));
+  return out->flags & (USN_DV_DROPPED | USN_DV_LONG) ? USN_ERANGE : USN_OK;
 }
 
 /* ---- packed delivery: byte-compact rings (usn_deliver_packed.hip) ----------- */

@@ -360,6 +360,50 @@ struct RoundDeliverArgs {
 };
 hipError_t launch_deliver_round(const RoundDeliverArgs &a, uint32_t pack_grid, hipStream_t stream);
 
+/* ---- ring delivery (usn_deliver_rings.hip): a poll round appended to the
+ * persistent, circular per-endpoint rings of a usn_ringset.  Three launches,
+ * whatever count is:
+ *   rings_plan_kernel    one workgroup: per (endpoint id, ring) the offered
+ *                        count (the round plan's rule), the id's free space
+ *                        from head / tail / ring_off, the tail-drop in
+ *                        registers (seg_acc, first, acc, drop), the next tails
+ *                        (scratch), the header, and the tile prefix over the
+ *                        receivers' ACCEPTED runs
+ *   rings_pack_kernel    device-sized grid; a tile is USN_DELIVER_TILE
+ *                        positions of one receiver's accepted run: the round
+ *                        pack's segment cuts and merge bounded by seg_acc, the
+ *                        output slot (first + position) & (S - 1) in the ring
+ *   rings_commit_kernel  one workgroup: tail[] = the next tails
+ * The per-ring fields are RoundDeliverArgs' (entries from count on repeat ring
+ * 0 with n = 0). */
+struct RingsDeliverArgs {
+  const uint8_t *frames[USN_ROUND_MAX];
+  uint64_t stride[USN_ROUND_MAX];
+  const uint64_t *offsets[USN_ROUND_MAX];
+  const uint16_t *lens[USN_ROUND_MAX];
+  const uint32_t *index[USN_ROUND_MAX];
+  const uint32_t *bin_off[USN_ROUND_MAX];
+  const usn_summary *summary[USN_ROUND_MAX];
+  uint32_t n[USN_ROUND_MAX];
+  uint32_t src[USN_ROUND_MAX];
+  const uint16_t *eptab;     /* as DeliverArgs */
+  uint8_t *out_frames;       /* the ring set's arrays: total slots */
+  uint16_t *out_lens;
+  uint32_t *out_src;
+  const uint32_t *ring_off;  /* [USN_DT_IDS + 1] */
+  const uint32_t *head;      /* [USN_DT_IDS] */
+  uint32_t *tail;            /* [USN_DT_IDS]: read by the plan, written by the commit */
+  uint32_t *first, *acc, *drop;   /* [USN_DT_IDS] each */
+  uint32_t *seg_acc;         /* [USN_ROUND_MAX * USN_DT_IDS] */
+  usn_ringset_hdr *hdr;
+  uint32_t *tile_pfx;        /* [USN_DT_IDS]: tiles of the accepted runs of the ids below */
+  uint32_t *next_tail;       /* [USN_DT_IDS]: first + acc, until the commit */
+  uint32_t total, slot;
+};
+/* scratch behind usn_ringset.hdr, from DELIVER_SCRATCH_OFF: tile_pfx, next_tail */
+constexpr size_t RINGS_SCRATCH_BYTES = 2 * DELIVER_SCRATCH_BYTES;
+hipError_t launch_deliver_rings(const RingsDeliverArgs &a, uint32_t pack_grid, hipStream_t stream);
+
 }  // namespace usn
 
 /* the same kernels at 512 threads per tile (a second compilation of

@@ -27,6 +27,7 @@ USN_ROUND_MAX = 8        # rings of one usn_deliver_round
 USN_DELIVER_TILE = 512   # output slots per pack tile of usn_deliver (usn_classify.h)
 DV_OVERFLOW, DV_LONG = 1, 2
 DV_OVERFLOW_BYTES = 4   # usn_deliver_packed: need_bytes > cap_bytes
+DV_DROPPED = 8          # usn_deliver_rings: an offered frame found its ring full
 R_WINDOW = 7
 PARITY_MASK = 0x00FFFFFF
 EP_NIC, EP_HOST, EP_PIPE, EP_UDS = 0, 1, 2, 3
@@ -104,6 +105,19 @@ class PDelivery(C.Structure):
                 ("hdr", C.c_void_p), ("cap", C.c_uint64), ("cap_bytes", C.c_uint64)]
 
 
+class RingSetHdr(C.Structure):
+    _fields_ = [("offered", C.c_uint64), ("dropped", C.c_uint64), ("accepted", C.c_uint32),
+                ("n_recv", C.c_uint32), ("flags", C.c_uint32), ("_r", C.c_uint32)]
+
+
+class RingSet(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("lens", C.c_void_p), ("src", C.c_void_p),
+                ("ring_off", C.c_void_p), ("head", C.c_void_p), ("tail", C.c_void_p),
+                ("first", C.c_void_p), ("acc", C.c_void_p), ("drop", C.c_void_p),
+                ("seg_acc", C.c_void_p), ("hdr", C.c_void_p), ("total", C.c_uint64),
+                ("slot", C.c_uint32), ("ready", C.c_uint32)]
+
+
 TILE_HDR_DTYPE = np.dtype([("n_frames", "<u2"), ("_r0", "<u2"), ("n_host", "<u2"),
                            ("bin_nic", "<u2"), ("class_count", "<u2", (4,)), ("last_state", "<u4"),
                            ("last_dst", "<u4"), ("last_idx", "<u4"), ("last_info", "<u4", (4,)),
@@ -178,6 +192,12 @@ def load(path: str | None = None):
         "usn_rdelivery_bind": ([P, SZ, U64, U32, C.POINTER(RDelivery)], I),
         "usn_deliver_round": ([P, P, P, U32, C.POINTER(RDelivery), P], I),
         "usn_deliver_round_info": ([P, C.POINTER(RDelivery), P, C.POINTER(DeliveryHdr)], I),
+        "usn_ringset_bytes": ([U64, U32], SZ),
+        "usn_ringset_bind": ([P, SZ, U64, U32, C.POINTER(RingSet)], I),
+        "usn_ringset_init": ([P, C.POINTER(RingSet), P, U32, P], I),
+        "usn_ringset_set_head": ([P, C.POINTER(RingSet), P, U32, P], I),
+        "usn_deliver_rings": ([P, P, P, U32, C.POINTER(RingSet), P], I),
+        "usn_deliver_rings_info": ([P, C.POINTER(RingSet), P, C.POINTER(RingSetHdr)], I),
     }
     optional = {"usn_set_frame_reader", "usn_ctx_create_group", "usn_ctx_replicas",
                 "usn_replica_select", "usn_replica_device", "usn_result_bytes_ep",
@@ -185,7 +205,9 @@ def load(path: str | None = None):
                 "usn_delivery_bind", "usn_deliver", "usn_deliver_info", "usn_pdelivery_bytes",
                 "usn_pdelivery_bind", "usn_deliver_packed", "usn_deliver_packed_info",
                 "usn_rdelivery_bytes", "usn_rdelivery_bind", "usn_deliver_round",
-                "usn_deliver_round_info"}   # A/B builds of older ABI versions lack these
+                "usn_deliver_round_info", "usn_ringset_bytes", "usn_ringset_bind", "usn_ringset_init",
+                "usn_ringset_set_head", "usn_deliver_rings",
+                "usn_deliver_rings_info"}   # A/B builds of older ABI versions lack these
     for name, (args, res) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -210,7 +232,9 @@ EXPORTED = ["usn_abi_version", "usn_strerror", "usn_last_hip_error", "usn_ctx_cr
             "usn_lists_wait", "usn_result_release", "usn_delivery_bytes", "usn_delivery_bind",
             "usn_deliver", "usn_deliver_info", "usn_pdelivery_bytes", "usn_pdelivery_bind",
             "usn_deliver_packed", "usn_deliver_packed_info", "usn_rdelivery_bytes",
-            "usn_rdelivery_bind", "usn_deliver_round", "usn_deliver_round_info"]
+            "usn_rdelivery_bind", "usn_deliver_round", "usn_deliver_round_info",
+            "usn_ringset_bytes", "usn_ringset_bind", "usn_ringset_init", "usn_ringset_set_head",
+            "usn_deliver_rings", "usn_deliver_rings_info"]
 
 
 def check(rc, what=""):
@@ -485,6 +509,16 @@ class Ctx:
         check(self.L.usn_deliver_round(self.h, C.cast(ba, C.c_void_p), C.cast(ra, C.c_void_p), n,
                                        C.byref(delivery.desc), stream), "usn_deliver_round")
 
+    def deliver_rings(self, batches, results, rs: "DeviceRingSet", stream=None):
+        """Append a poll round to the persistent endpoint rings of `rs`
+        (usn_deliver_rings): deliver_round's rings and order; each receiver takes
+        what its ring has room for and drops the rest, tails move last."""
+        n = len(batches)
+        ba = (Batch * n)(*[b.desc for b in batches])
+        ra = (Result * n)(*[r.desc for r in results])
+        check(self.L.usn_deliver_rings(self.h, C.cast(ba, C.c_void_p), C.cast(ra, C.c_void_p), n,
+                                       C.byref(rs.desc), stream), "usn_deliver_rings")
+
 
 class DeviceBatch:
     """Frames + lengths resident in HBM (one drained rx ring)."""
@@ -707,6 +741,91 @@ class DeviceRoundDelivery(DeviceDelivery):
         k0, k1 = int(so[0]), int(so[-1])
         rings = np.repeat(np.arange(USN_ROUND_MAX, dtype=np.uint8), np.diff(so))
         return self.src(k0, k1), self.lens(k0, k1), self.slots(k0, k1), rings
+
+
+class DeviceRingSet:
+    """One usn_ringset: a circular ring of ring_slots[e] slots (0 or a power of
+    two) of `slot` bytes per endpoint id e, with free-running head / tail
+    counters.  `poison` fills the whole allocation before usn_ringset_init."""
+
+    def __init__(self, ctx: Ctx, ring_slots, slot: int, poison: int | None = None):
+        self.ctx = ctx
+        sizes = np.ascontiguousarray(ring_slots, dtype=np.uint32)
+        self.total = self.cap = max(int(sizes.astype(np.int64).sum()), 1)   # cap: DeviceDelivery's readers
+        self.slot = int(slot)
+        nbytes = ctx.L.usn_ringset_bytes(self.total, self.slot)
+        if nbytes == 0:
+            raise UsnError("usn_ringset_bytes: bad total %d or slot %d" % (self.total, self.slot))
+        self.buf = ctx.alloc(nbytes)
+        self.desc = RingSet()
+        check(ctx.L.usn_ringset_bind(self.buf.ptr, nbytes, self.total, self.slot, C.byref(self.desc)),
+              "usn_ringset_bind")
+        if poison is not None:
+            check(ctx.L.usn_memset_d(ctx.h, self.buf.ptr, poison, nbytes, None), "usn_memset_d")
+            ctx.sync()
+        check(ctx.L.usn_ringset_init(ctx.h, C.byref(self.desc), sizes.ctypes.data, sizes.size, None),
+              "usn_ringset_init")
+        self.off = np.concatenate([[0], np.cumsum(sizes.astype(np.int64))])   # ring e: [off[e], off[e + 1])
+
+    def set_head(self, head, stream=None):
+        """absolute head counters of ids 0 .. len(head) - 1 (usn_ringset_set_head)"""
+        head = np.ascontiguousarray(head, dtype=np.uint32)
+        check(self.ctx.L.usn_ringset_set_head(self.ctx.h, C.byref(self.desc), head.ctypes.data,
+                                              head.size, stream), "usn_ringset_set_head")
+
+    def set_counters(self, head, tail):
+        """head and tail of ids 0 .. len - 1 by a plain device copy (tests and tools)"""
+        for ptr, v in ((self.desc.head, head), (self.desc.tail, tail)):
+            self.buf.upload(np.ascontiguousarray(v, dtype=np.uint32), offset=ptr - self.buf.ptr)
+
+    def info(self, stream=None, strict=True) -> RingSetHdr:
+        """The header after the call on `stream` finished.  strict: raise on
+        USN_DV_DROPPED / USN_DV_LONG (USN_ERANGE); else return it with .status."""
+        h = RingSetHdr()
+        rc = self.ctx.L.usn_deliver_rings_info(self.ctx.h, C.byref(self.desc), stream, C.byref(h))
+        if strict or rc != USN_ERANGE:
+            check(rc, "usn_deliver_rings_info")
+        h.status = rc
+        return h
+
+    _get = DeviceDelivery._get
+
+    def _ids(self, ptr) -> np.ndarray:
+        return self._get(ptr, np.uint32, USN_MAX_ENDPOINTS + 1)
+
+    def head(self) -> np.ndarray:
+        return self._ids(self.desc.head)
+
+    def tail(self) -> np.ndarray:
+        return self._ids(self.desc.tail)
+
+    def first(self) -> np.ndarray:
+        return self._ids(self.desc.first)
+
+    def acc(self) -> np.ndarray:
+        return self._ids(self.desc.acc)
+
+    def drop(self) -> np.ndarray:
+        return self._ids(self.desc.drop)
+
+    def seg_acc(self) -> np.ndarray:
+        """[id, ring]: accepted frames of segment (e, k) in the last call"""
+        return self._get(self.desc.seg_acc, np.uint32,
+                         USN_ROUND_MAX * (USN_MAX_ENDPOINTS + 1)).reshape(-1, USN_ROUND_MAX)
+
+    lens, src, slots = DeviceDelivery.lens, DeviceDelivery.src, DeviceDelivery.slots   # of slots [k0, k1)
+
+    def ring(self, e: int):
+        """(lens, src_idx, bytes[k, slot]) of ring e from head to tail, in consumer order"""
+        k0, k1 = int(self.off[e]), int(self.off[e + 1])
+        h, t = int(self.head()[e]), int(self.tail()[e])
+        pos = (h + np.arange(min((t - h) & 0xFFFFFFFF, k1 - k0), dtype=np.int64)) & (k1 - k0 - 1)
+        return self.lens(k0, k1)[pos], self.src(k0, k1)[pos], self.slots(k0, k1)[pos]
+
+    def free(self):
+        if self.buf is not None:
+            self.buf.free()
+            self.buf = None
 
 
 class DevicePackedDelivery:
