@@ -648,6 +648,88 @@ int usn_deliver_rings(usn_ctx *ctx, const usn_batch *b, const usn_result *r, uin
 int usn_deliver_rings_info(usn_ctx *ctx, const usn_ringset *rs, void *hip_stream,
                            usn_ringset_hdr *host_out);
 
+/* ---- ring drain: the endpoint rings' queued frames gathered on the device ----
+ * The consumer of a usn_ringset.  One call takes up to budget[e] frames from
+ * every ring, oldest first, lays them byte-compact in one region
+ * (usn_deliver_packed's layout) so that ONE copy of frames[0, need_bytes)
+ * carries the whole round to the host, and advances the heads.
+ *
+ * Per id e, with S = ring_off[e+1] - ring_off[e], f = tail[e] - head[e] in
+ * 32-bit arithmetic and h = head[e] as found: avail = f <= S ? f : 0.  A ring
+ * with S > 0 and f > S has corrupt counters: it is not drained and sets
+ * USN_DR_BADCOUNT (it would be full for the producer and empty for the
+ * consumer for good).  want = min(avail, budget[e]); the slot capacity is
+ * handed out in id order, take[e] = min(want[e], cap - min(cap, sum of want
+ * below e)); left[e] = avail - take[e], and any left > 0 sets USN_DR_MORE;
+ * from[e] = h.  Output slots [ep_off[e], ep_off[e+1]) hold ring positions h,
+ * h + 1, ... in that order, ids ascending.  Output slot k, taken from ring
+ * slot q = ring_off[e] + ((h + j) & (S - 1)), has lens[k] = rs->lens[q] (the
+ * true length) and src[k] = rs->src[q]; with clen = min(lens[k], rs->slot) its
+ * bytes lie at frames + 16 * off16[k] and occupy ceil16(clen) bytes: [0, clen)
+ * the ring slot's, [clen, ceil16(clen)) zero whatever the slot held.  Frames
+ * lie back to back over all ids, ep_boff is monotone as in usn_deliver_packed,
+ * and USN_DV_LONG is set when a selected frame has lens > rs->slot.
+ *
+ * Bytes are all or nothing.  need_bytes = the sum of ceil16(clen) over the
+ * selected frames.  need_bytes > cap_bytes: USN_DV_OVERFLOW_BYTES; every
+ * metadata array and need_bytes are valid and complete, no byte of `frames` is
+ * written and NO HEAD MOVES.  Otherwise every byte of frames[0, need_bytes) is
+ * written, nothing past it, and head[e] += take[e].  Ring slots, rs->lens,
+ * rs->src and tail are never written.
+ *
+ * The heads move in the call's third launch, before its last launch has read
+ * the slots they release.  That is safe only because usn_rings_drain must be
+ * stream-ordered with the appends (usn_deliver_rings) and head updates
+ * (usn_ringset_set_head) of the same ring set: no producer runs inside the
+ * call.  A producer ordered by anything weaker than the stream (or an event
+ * recorded behind the whole call) must not look at head[]. */
+#define USN_HAS_RINGS_DRAIN 1
+#define USN_DR_MORE 16u       /* a ring keeps queued frames after the call (budget or capacity) */
+#define USN_DR_BADCOUNT 32u   /* a ring's tail - head exceeds its size: not drained */
+typedef struct {
+  uint64_t need_bytes, cap_bytes;   /* sum of ceil16(clen) over the selected frames / the region's size */
+  uint32_t selected;    /* sum of take[] */
+  uint32_t taken;       /* selected, or 0 on byte overflow (no head moved) */
+  uint32_t n_recv;      /* ids with take > 0 */
+  uint32_t flags;       /* USN_DV_OVERFLOW_BYTES, USN_DV_LONG, USN_DR_MORE, USN_DR_BADCOUNT */
+} usn_drain_hdr;
+typedef struct {
+  uint8_t  *frames;     /* cap_bytes; output slot k's frame at frames + 16 * off16[k] */
+  uint32_t *off16;      /* cap */
+  uint16_t *lens;       /* cap: true lengths */
+  uint32_t *src;        /* cap */
+  uint32_t *ep_off;     /* USN_MAX_ENDPOINTS + 2: slots of id e = [ep_off[e], ep_off[e+1]) */
+  uint64_t *ep_boff;    /* USN_MAX_ENDPOINTS + 2: bytes of id e = [ep_boff[e], ep_boff[e+1]) */
+  uint32_t *budget;     /* USN_MAX_ENDPOINTS + 1, input: the most frames to take from ring e */
+  uint32_t *from;       /* per id: head[e] before this call */
+  uint32_t *take;       /* per id: frames selected by this call */
+  uint32_t *left;       /* per id: frames still queued behind them */
+  usn_drain_hdr *hdr;   /* followed by the kernels' scratch */
+  uint64_t cap, cap_bytes;
+} usn_drain;
+/* usn_pdelivery_bytes / usn_pdelivery_bind's argument rules and 256-byte
+ * aligned carving: cap_slots in [1, 2^32), cap_bytes a non-zero multiple of 16
+ * of at most 2^36 - 16; 0 / USN_EINVAL for such arguments, USN_ERANGE when
+ * `bytes` is too small.  Host memory is accepted for layout checks. */
+size_t usn_drain_bytes(uint64_t cap_slots, uint64_t cap_bytes);
+int usn_drain_bind(void *dev_mem, size_t bytes, uint64_t cap_slots, uint64_t cap_bytes, usn_drain *out);
+/* As usn_ringset_set_head: copies the budgets of ids below n_ids on
+ * `hip_stream` (ids from n_ids on get 0) and returns when the caller's array
+ * may be reused.  The budgets stay until the next call: a consumer sets them
+ * once. */
+int usn_drain_set_budget(usn_ctx *ctx, usn_drain *d, const uint32_t *budget, uint32_t n_ids,
+                         void *hip_stream);
+/* Four launches on `hip_stream` (plan, sum, scan with the commit, copy); no
+ * host synchronisation and no copy in the steady state.  USN_EINVAL: a null
+ * pointer, a ring set that is not ready, a drain that was not bound;
+ * USN_ENODEV: a USN_HOST_ONLY context. */
+int usn_rings_drain(usn_ctx *ctx, usn_ringset *rs, usn_drain *d, void *hip_stream);
+/* Synchronises `hip_stream` and copies the header to the host: USN_ERANGE when
+ * USN_DV_OVERFLOW_BYTES or USN_DR_BADCOUNT is set (host_out is filled all the
+ * same).  USN_DR_MORE and USN_DV_LONG alone return 0: they are the normal
+ * state of a budgeted consumer. */
+int usn_rings_drain_info(usn_ctx *ctx, const usn_drain *d, void *hip_stream, usn_drain_hdr *host_out);
+
 /* Forget the carried decision cache of one endpoint (last_pkt = None). */
 int usn_cache_clear(usn_ctx *ctx, uint16_t endpoint);
 

@@ -26,8 +26,14 @@ once with rings ample enough that nothing drops, once with rings of about half
 of what each endpoint is offered.  Heads are reset to the tails between calls
 (a device copy outside the timed span), so the rings never fill up.
 
+--drain times usn_rings_drain (the consumer: four launches) with full budgets on
+--rings' ample ring sets next to the usn_deliver_rings append that filled them
+and to ONE device-to-device copy of need_bytes, the three alternating in blocks.
+Every timed drain follows an append and every timed append a drain, each
+outside the other's timed span: the drain moves the heads itself.
+
 usage: python tools/deliver_bench.py [--config c5] [--frames N] [--multi 2] [--rounds 2]
-                                     [--launches 120] [--slot 64] [--packed | --round | --rings]
+                                     [--launches 120] [--slot 64] [--packed | --round | --rings | --drain]
                                      [--json out.json]
 """
 import argparse
@@ -55,6 +61,7 @@ def main():
     ap.add_argument("--packed", action="store_true")
     ap.add_argument("--round", action="store_true")
     ap.add_argument("--rings", action="store_true")
+    ap.add_argument("--drain", action="store_true")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     n, Q, R = a.frames, a.multi, a.rounds
@@ -99,9 +106,11 @@ def main():
         for k in range(Q):
             assert hip.hipMemcpyDtoDAsync(pds[r][k].desc.frames, copy_src[r][k], need_b[k], s) == 0
 
-    def timed(fn, count, after=None):
+    def timed(fn, count, after=None, before=None):
         evs = [(ctx.event(), ctx.event()) for _ in range(count)]
         for i, (x, y) in enumerate(evs):
+            if before:
+                before(i % R)
             ctx.record(x, s)
             fn(i % R)
             ctx.record(y, s)
@@ -141,6 +150,8 @@ def main():
         return round_mode(a, ctx, s, hip, bs, rs, dvs, need, deliver, timed, block)
     if a.rings:
         return rings_mode(a, ctx, s, hip, bs, rs, need, timed, block)
+    if a.drain:
+        return drain_mode(a, ctx, s, hip, bs, rs, need, timed, block)
     dl_us, cp_us = [], []
     while len(dl_us) < a.launches:
         dl_us += timed(deliver, block)
@@ -283,6 +294,74 @@ def rings_mode(a, ctx, s, hip, bs, rs, need, timed, block):
     out["rings_over_copy"] = round(out["rings_us"] / out["d2d_copy_us"], 2)
     out["rings_half_over_rings"] = round(out["rings_half_us"] / out["rings_us"], 3)
     out["rings_half_over_copy"] = round(out["rings_half_us"] / out["d2d_copy_half_us"], 2)
+    print(json.dumps(out), flush=True)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+    ctx.close()
+
+
+def drain_mode(a, ctx, s, hip, bs, rs, need, timed, block):
+    """usn_rings_drain with full budgets on ample ring sets against the usn_deliver_rings append of
+    the same frames and one copy of need_bytes"""
+    n, Q, R = a.frames, a.multi, a.rounds
+    rd = lib.DeviceRoundDelivery(ctx, n * Q, a.slot)
+    ctx.deliver_round(bs[0], rs[0], rd, s)
+    assert rd.info(s).need == need
+    cnt = np.diff(rd.ep_off().astype(np.int64), append=need)   # what a call offers each endpoint
+    rd.free()
+    ids = int(np.flatnonzero(cnt)[-1]) + 1
+    ample = np.where(cnt[:ids] > 0, 2 ** np.ceil(np.log2(np.maximum(cnt[:ids], 1))), 0).astype(np.uint32)
+    sets = [lib.DeviceRingSet(ctx, ample, a.slot) for _ in range(R)]
+    drs = [lib.DeviceDrain(ctx, need, need * a.slot) for _ in range(R)]
+    for d in drs:
+        d.set_budget([0xFFFFFFFF] * ids)
+    cp_src = ctx.alloc(need * a.slot)
+
+    def append(r):
+        ctx.deliver_rings(bs[r], rs[r], sets[r], s)
+
+    def drain(r):
+        ctx.drain_rings(sets[r], drs[r], s)
+
+    # the first append's rings against what the drain takes out of them: two endpoints
+    append(0)
+    assert (sets[0].info(s).accepted, sets[0].info(s).flags) == (need, 0), "the ample rings dropped or truncated"
+    queued = {e: sets[0].ring(e) for e in (2, ids - 1)}
+    drain(0)
+    h = drs[0].info(s)
+    assert (h.selected, h.taken, h.flags) == (need, need, 0) and not sets[0].ring(2)[0].size
+    need_b = int(h.need_bytes)
+    off, boff = drs[0].ep_off(), drs[0].ep_boff()
+    for e, (lens, src, slots) in queued.items():
+        k0, k1 = int(off[e]), int(off[e + 1])
+        assert np.array_equal(drs[0].lens(k0, k1), lens) and np.array_equal(drs[0].src(k0, k1), src)
+        want = np.concatenate([row[:(int(ln) + 15) // 16 * 16] for row, ln in zip(slots, lens)])
+        assert np.array_equal(drs[0].bytes(int(boff[e]), int(boff[e + 1])), want), "ring %d drained differently" % e
+
+    def copy(r):
+        assert hip.hipMemcpyDtoDAsync(drs[r].desc.frames, cp_src.ptr, need_b, s) == 0
+
+    for r in list(range(1, R)) + list(range(R)) * 2:   # warm-up; every set ends drained
+        append(r)
+        drain(r)
+        copy(r)
+    us = {k: [] for k in ("drain", "append", "d2d_copy")}
+    while len(us["drain"]) < a.launches:
+        us["drain"] += timed(drain, block, before=append)
+        us["append"] += timed(append, block, after=drain)
+        us["d2d_copy"] += timed(copy, block)
+    for r in range(R):   # the last calls took everything
+        h = drs[r].info(s)
+        assert (h.taken, h.need_bytes, h.flags) == (need, need_b, 0) and sets[r].info(s).accepted == need
+    out = dict(config=a.config, frames_per_call=n * Q, rings=Q, slot=a.slot, drained_slots=need,
+               need_bytes=need_b, endpoints_with_a_ring=int((ample > 0).sum()), ring_slots=int(ample.sum()),
+               launches=len(us["drain"]), launches_per_call_drain=4, launches_per_call_append=3)
+    for k, v in us.items():
+        out.update(stats(v, k))
+    out["drain_over_copy"] = round(out["drain_us"] / out["d2d_copy_us"], 2)
+    out["append_over_copy"] = round(out["append_us"] / out["d2d_copy_us"], 2)
+    out["drain_over_append"] = round(out["drain_us"] / out["append_us"], 3)
     print(json.dumps(out), flush=True)
     if a.json:
         with open(a.json, "w") as fh:

@@ -4147,6 +4147,131 @@ int usn_deliver_rings_info(usn_ctx *c, const usn_ringset *rs, void *stream, usn_
   return out->flags & (USN_DV_DROPPED | USN_DV_LONG) ? USN_ERANGE : USN_OK;
 }
 
+/* ---- ring drain: the consumer of a ring set (usn_rings_drain.hip) ----------- */
+struct DrainLayout {
+  size_t frames, off16, lens, src, ep_off, ep_boff, budget, from, take, left, hdr, total;
+};
+/* usn_pdelivery's rules and order; the per-id arrays between ep_boff and the header */
+static bool drain_layout(uint64_t cap, uint64_t cap_bytes, DrainLayout &L) {
+  if (cap == 0 || cap > 0xFFFFFFFFull) return false;
+  if (cap_bytes == 0 || cap_bytes % 16 != 0 || cap_bytes > (1ull << 36) - 16) return false;   // off16 is 32 bits
+  const size_t ids = (size_t)USN_DT_IDS * 4;
+  size_t off = 0;
+  L.frames = off; off = align256(off + (size_t)cap_bytes);
+  L.off16 = off; off = align256(off + (size_t)cap * 4);
+  L.lens = off; off = align256(off + (size_t)cap * 2);
+  L.src = off; off = align256(off + (size_t)cap * 4);
+  L.ep_off = off; off = align256(off + ids + 4);
+  L.ep_boff = off; off = align256(off + 2 * ids + 8);
+  L.budget = off; off = align256(off + ids);
+  L.from = off; off = align256(off + ids);
+  L.take = off; off = align256(off + ids);
+  L.left = off; off = align256(off + ids);
+  L.hdr = off; off = align256(off + usn::DELIVER_SCRATCH_OFF + usn::drain_scratch_bytes(cap));
+  L.total = off;
+  return true;
+}
+
+size_t usn_drain_bytes(uint64_t cap_slots, uint64_t cap_bytes) {
+  DrainLayout L;
+  return drain_layout(cap_slots, cap_bytes, L) ? L.total : 0;
+}
+
+int usn_drain_bind(void *mem, size_t bytes, uint64_t cap_slots, uint64_t cap_bytes, usn_drain *out) {
+  DrainLayout L;
+  if (!mem || !out || ((uintptr_t)mem & 15) != 0 || !drain_layout(cap_slots, cap_bytes, L)) return USN_EINVAL;
+  if (bytes < L.total) return USN_ERANGE;
+  uint8_t *b = static_cast<uint8_t *>(mem);
+  auto u32 = [b](size_t off) { return reinterpret_cast<uint32_t *>(b + off); };
+  out->frames = b + L.frames;
+  out->off16 = u32(L.off16);
+  out->lens = reinterpret_cast<uint16_t *>(b + L.lens);
+  out->src = u32(L.src);
+  out->ep_off = u32(L.ep_off);
+  out->ep_boff = reinterpret_cast<uint64_t *>(b + L.ep_boff);
+  out->budget = u32(L.budget);
+  out->from = u32(L.from);
+  out->take = u32(L.take);
+  out->left = u32(L.left);
+  out->hdr = reinterpret_cast<usn_drain_hdr *>(b + L.hdr);
+  out->cap = cap_slots;
+  out->cap_bytes = cap_bytes;
+  return USN_OK;
+}
+
+/* what the drain entry points ask of a bound drain */
+static bool drain_ok(const usn_drain *d) {
+  if (!d->frames || !d->off16 || !d->lens || !d->src || !d->ep_off || !d->ep_boff || !d->budget || !d->from ||
+      !d->take || !d->left || !d->hdr)
+    return false;
+  if (d->cap == 0 || d->cap > 0xFFFFFFFFull || d->cap_bytes == 0 || d->cap_bytes % 16 != 0 ||
+      d->cap_bytes > (1ull << 36) - 16)
+    return false;
+  const uintptr_t vec = (uintptr_t)d->frames | (uintptr_t)d->ep_off | (uintptr_t)d->ep_boff |
+                        (uintptr_t)d->budget | (uintptr_t)d->from | (uintptr_t)d->take | (uintptr_t)d->left |
+                        (uintptr_t)d->hdr;
+  return (vec & 15) == 0;   // the kernels' 16-byte loads and stores
+}
+
+int usn_drain_set_budget(usn_ctx *c, usn_drain *d, const uint32_t *budget, uint32_t n_ids, void *stream) {
+  if (!c || !d || !d->budget || (!budget && n_ids) || n_ids > USN_MAX_ENDPOINTS) return USN_EINVAL;
+  if (c->device < 0) return USN_ENODEV;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(d->budget + n_ids, 0, (size_t)(USN_DT_IDS - n_ids) * 4, st));   // ids from n_ids on: 0
+  if (n_ids) HIPCHK(hipMemcpyAsync(d->budget, budget, (size_t)n_ids * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));   // the caller's array may be reused
+  return USN_OK;
+}
+
+int usn_rings_drain(usn_ctx *c, usn_ringset *rs, usn_drain *d, void *stream) {
+  if (!c || !rs || !d) return USN_EINVAL;
+  if (!ringset_ok(rs) || !rs->ready || !drain_ok(d)) return USN_EINVAL;
+  if (c->reps.empty() || c->device < 0) return USN_ENODEV;
+  std::lock_guard<std::mutex> g(c->mu);
+  /* the replica usn_ringset_init laid the ring set out on: the selected one */
+  const Replica &R = c->reps[c->sel < c->reps.size() ? c->sel : 0];
+  HIPCHK(hipSetDevice(R.device));
+  usn::DrainArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.frames = rs->frames;
+  a.lens = rs->lens;
+  a.src = rs->src;
+  a.ring_off = rs->ring_off;
+  a.head = rs->head;
+  a.tail = rs->tail;
+  a.out_frames = d->frames;
+  a.out_off16 = d->off16;
+  a.out_lens = d->lens;
+  a.out_src = d->src;
+  a.ep_off = d->ep_off;
+  a.ep_boff = d->ep_boff;
+  a.budget = d->budget;
+  a.from = d->from;
+  a.take = d->take;
+  a.left = d->left;
+  a.hdr = d->hdr;
+  uint8_t *scratch = reinterpret_cast<uint8_t *>(d->hdr);
+  a.tile_pfx = reinterpret_cast<uint32_t *>(scratch + usn::DELIVER_SCRATCH_OFF);
+  a.next_head = a.tile_pfx + USN_DT_IDS;
+  a.tile_base = reinterpret_cast<uint64_t *>(scratch + usn::DRAIN_BASE_OFF);
+  a.tile_b16 = reinterpret_cast<uint32_t *>(a.tile_base + usn::pdeliver_max_tiles(d->cap));
+  a.total = (uint32_t)rs->total;
+  a.slot = rs->slot;
+  a.cap = (uint32_t)d->cap;
+  a.cap_bytes = d->cap_bytes;
+  // the sum and copy grids: what the device holds at once, as the other delivery grids
+  HIPCHK(usn::launch_rings_drain(a, (uint32_t)std::max(R.n_cu, 1) * 8u, (hipStream_t)stream));
+  return USN_OK;
+}
+
+int usn_rings_drain_info(usn_ctx *c, const usn_drain *d, void *stream, usn_drain_hdr *out) {
+  if (!c || !d || !d->hdr || !out) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  HIPCHK(hipMemcpy(out, d->hdr, sizeof *out, hipMemcpyDeviceToHost));
+  return out->flags & (USN_DV_OVERFLOW_BYTES | USN_DR_BADCOUNT) ? USN_ERANGE : USN_OK;
+}
+
 /* ---- packed delivery: byte-compact rings (usn_deliver_packed.hip) ----------- */
 struct PDeliveryLayout {
   size_t frames, off16, lens, src, ep_off, ep_boff, hdr, total;

@@ -404,6 +404,54 @@ struct RingsDeliverArgs {
 constexpr size_t RINGS_SCRATCH_BYTES = 2 * DELIVER_SCRATCH_BYTES;
 hipError_t launch_deliver_rings(const RingsDeliverArgs &a, uint32_t pack_grid, hipStream_t stream);
 
+/* ---- ring drain (usn_rings_drain.hip): the consumer of a usn_ringset.  Up to
+ * budget[e] of ring e's oldest frames, ids ascending, byte-compact in
+ * usn_deliver_packed's layout, and the heads moved.  Four launches:
+ *   drain_plan_kernel  one workgroup: avail / want per id from ring_off, head,
+ *                      tail and budget, the capacity handed out in id order
+ *                      (from, take, left, ep_off), the next heads (scratch),
+ *                      the header, and the tile prefix over the selected runs
+ *   drain_sum_kernel   device-sized grid: per tile its ring slots' lens read
+ *                      coalesced, the 16-byte pieces (sum of ceil16(min(len,
+ *                      slot)) / 16) into tile_b16[t]
+ *   drain_scan_kernel  one workgroup: the packed scan (tile_base, ep_boff,
+ *                      need_bytes, the byte-overflow flag) and, when the call
+ *                      fits, the commit: head[] = the next heads
+ *   drain_copy_kernel  device-sized grid: per tile lens / src read from the
+ *                      ring, the pieces' scan in LDS, off16 / lens / src, and
+ *                      the output-stationary gather out of the ring slots */
+struct DrainArgs {
+  const uint8_t *frames;     /* the ring set's arrays: total slots, read only */
+  const uint16_t *lens;
+  const uint32_t *src;
+  const uint32_t *ring_off;  /* [USN_DT_IDS + 1] */
+  uint32_t *head;            /* [USN_DT_IDS]: read by the plan, written by the scan's commit */
+  const uint32_t *tail;      /* [USN_DT_IDS] */
+  uint8_t *out_frames;
+  uint32_t *out_off16;
+  uint16_t *out_lens;
+  uint32_t *out_src;
+  uint32_t *ep_off;          /* [USN_DT_IDS + 1] */
+  uint64_t *ep_boff;         /* [USN_DT_IDS + 1] */
+  const uint32_t *budget;    /* [USN_DT_IDS] */
+  uint32_t *from, *take, *left;   /* [USN_DT_IDS] each */
+  usn_drain_hdr *hdr;
+  uint32_t *tile_pfx;        /* [USN_DT_IDS]: tiles of the selected runs of the ids below */
+  uint32_t *next_head;       /* [USN_DT_IDS]: from + take, until the commit */
+  uint64_t *tile_base;       /* [max tiles]: 16-byte pieces before tile t */
+  uint32_t *tile_b16;        /* [max tiles]: 16-byte pieces of tile t */
+  uint32_t total, slot;      /* the ring set's */
+  uint32_t cap;
+  uint64_t cap_bytes;
+};
+/* scratch behind usn_drain.hdr, from DELIVER_SCRATCH_OFF: tile_pfx, next_head,
+ * then tile_base and tile_b16 for pdeliver_max_tiles(cap) tiles */
+constexpr size_t DRAIN_BASE_OFF = DELIVER_SCRATCH_OFF + 2 * DELIVER_SCRATCH_BYTES;   /* 8-byte aligned */
+constexpr size_t drain_scratch_bytes(uint64_t cap) {
+  return 2 * DELIVER_SCRATCH_BYTES + pdeliver_max_tiles(cap) * 12;
+}
+hipError_t launch_rings_drain(const DrainArgs &a, uint32_t grid, hipStream_t stream);
+
 }  // namespace usn
 
 /* the same kernels at 512 threads per tile (a second compilation of

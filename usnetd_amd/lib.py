@@ -28,6 +28,8 @@ USN_DELIVER_TILE = 512   # output slots per pack tile of usn_deliver (usn_classi
 DV_OVERFLOW, DV_LONG = 1, 2
 DV_OVERFLOW_BYTES = 4   # usn_deliver_packed: need_bytes > cap_bytes
 DV_DROPPED = 8          # usn_deliver_rings: an offered frame found its ring full
+DR_MORE = 16            # usn_rings_drain: a ring keeps queued frames after the call
+DR_BADCOUNT = 32        # usn_rings_drain: a ring's tail - head exceeds its size (not drained)
 R_WINDOW = 7
 PARITY_MASK = 0x00FFFFFF
 EP_NIC, EP_HOST, EP_PIPE, EP_UDS = 0, 1, 2, 3
@@ -118,6 +120,19 @@ class RingSet(C.Structure):
                 ("slot", C.c_uint32), ("ready", C.c_uint32)]
 
 
+class DrainHdr(C.Structure):
+    _fields_ = [("need_bytes", C.c_uint64), ("cap_bytes", C.c_uint64), ("selected", C.c_uint32),
+                ("taken", C.c_uint32), ("n_recv", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class Drain(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("off16", C.c_void_p), ("lens", C.c_void_p),
+                ("src", C.c_void_p), ("ep_off", C.c_void_p), ("ep_boff", C.c_void_p),
+                ("budget", C.c_void_p), ("from_", C.c_void_p), ("take", C.c_void_p),
+                ("left", C.c_void_p), ("hdr", C.c_void_p), ("cap", C.c_uint64),
+                ("cap_bytes", C.c_uint64)]
+
+
 TILE_HDR_DTYPE = np.dtype([("n_frames", "<u2"), ("_r0", "<u2"), ("n_host", "<u2"),
                            ("bin_nic", "<u2"), ("class_count", "<u2", (4,)), ("last_state", "<u4"),
                            ("last_dst", "<u4"), ("last_idx", "<u4"), ("last_info", "<u4", (4,)),
@@ -198,6 +213,11 @@ def load(path: str | None = None):
         "usn_ringset_set_head": ([P, C.POINTER(RingSet), P, U32, P], I),
         "usn_deliver_rings": ([P, P, P, U32, C.POINTER(RingSet), P], I),
         "usn_deliver_rings_info": ([P, C.POINTER(RingSet), P, C.POINTER(RingSetHdr)], I),
+        "usn_drain_bytes": ([U64, U64], SZ),
+        "usn_drain_bind": ([P, SZ, U64, U64, C.POINTER(Drain)], I),
+        "usn_drain_set_budget": ([P, C.POINTER(Drain), P, U32, P], I),
+        "usn_rings_drain": ([P, C.POINTER(RingSet), C.POINTER(Drain), P], I),
+        "usn_rings_drain_info": ([P, C.POINTER(Drain), P, C.POINTER(DrainHdr)], I),
     }
     optional = {"usn_set_frame_reader", "usn_ctx_create_group", "usn_ctx_replicas",
                 "usn_replica_select", "usn_replica_device", "usn_result_bytes_ep",
@@ -207,7 +227,8 @@ def load(path: str | None = None):
                 "usn_rdelivery_bytes", "usn_rdelivery_bind", "usn_deliver_round",
                 "usn_deliver_round_info", "usn_ringset_bytes", "usn_ringset_bind", "usn_ringset_init",
                 "usn_ringset_set_head", "usn_deliver_rings",
-                "usn_deliver_rings_info"}   # A/B builds of older ABI versions lack these
+                "usn_deliver_rings_info", "usn_drain_bytes", "usn_drain_bind", "usn_drain_set_budget",
+                "usn_rings_drain", "usn_rings_drain_info"}   # A/B builds of older ABI versions lack these
     for name, (args, res) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -234,7 +255,8 @@ EXPORTED = ["usn_abi_version", "usn_strerror", "usn_last_hip_error", "usn_ctx_cr
             "usn_deliver_packed", "usn_deliver_packed_info", "usn_rdelivery_bytes",
             "usn_rdelivery_bind", "usn_deliver_round", "usn_deliver_round_info",
             "usn_ringset_bytes", "usn_ringset_bind", "usn_ringset_init", "usn_ringset_set_head",
-            "usn_deliver_rings", "usn_deliver_rings_info"]
+            "usn_deliver_rings", "usn_deliver_rings_info", "usn_drain_bytes", "usn_drain_bind",
+            "usn_drain_set_budget", "usn_rings_drain", "usn_rings_drain_info"]
 
 
 def check(rc, what=""):
@@ -518,6 +540,12 @@ class Ctx:
         ra = (Result * n)(*[r.desc for r in results])
         check(self.L.usn_deliver_rings(self.h, C.cast(ba, C.c_void_p), C.cast(ra, C.c_void_p), n,
                                        C.byref(rs.desc), stream), "usn_deliver_rings")
+
+    def drain_rings(self, rs: "DeviceRingSet", dr: "DeviceDrain", stream=None):
+        """Take up to dr's budgets of the oldest queued frames of every ring of
+        `rs`, byte-compact into `dr`, and move the heads (usn_rings_drain):
+        asynchronous on `stream`, which must also order the appends to `rs`."""
+        check(self.L.usn_rings_drain(self.h, C.byref(rs.desc), C.byref(dr.desc), stream), "usn_rings_drain")
 
 
 class DeviceBatch:
@@ -890,3 +918,69 @@ class DevicePackedDelivery:
         if self.buf is not None:
             self.buf.free()
             self.buf = None
+
+
+class DeviceDrain:
+    """One usn_drain: what a usn_rings_drain call takes out of a ring set --
+    cap_bytes of frames lying back to back (each padded to 16 bytes), off16[] /
+    lens[] / src[] per output slot, the per-id slot and byte offsets, the
+    budgets (input), from / take / left per id and the header.  `poison` as for
+    DeviceDelivery; the budgets start at 0 either way."""
+
+    def __init__(self, ctx: Ctx, cap_slots: int, cap_bytes: int, poison: int | None = None):
+        self.ctx = ctx
+        self.cap = int(cap_slots)
+        self.cap_bytes = int(cap_bytes)
+        nbytes = ctx.L.usn_drain_bytes(self.cap, self.cap_bytes)
+        if nbytes == 0:
+            raise UsnError("usn_drain_bytes: bad capacity %d slots / %d bytes" % (self.cap, self.cap_bytes))
+        self.buf = ctx.alloc(nbytes)
+        self.desc = Drain()
+        check(ctx.L.usn_drain_bind(self.buf.ptr, nbytes, self.cap, self.cap_bytes, C.byref(self.desc)),
+              "usn_drain_bind")
+        if poison is not None:
+            check(ctx.L.usn_memset_d(ctx.h, self.buf.ptr, poison, nbytes, None), "usn_memset_d")
+            ctx.sync()
+        self.set_budget([])
+
+    def set_budget(self, budget, stream=None):
+        """the most frames to take from ring 0 .. len(budget) - 1 per call; the other ids get 0"""
+        budget = np.ascontiguousarray(budget, dtype=np.uint32)
+        check(self.ctx.L.usn_drain_set_budget(self.ctx.h, C.byref(self.desc), budget.ctypes.data,
+                                              budget.size, stream), "usn_drain_set_budget")
+
+    def info(self, stream=None, strict=True) -> DrainHdr:
+        """The header after the drain on `stream` finished.  strict: raise on
+        USN_DV_OVERFLOW_BYTES / USN_DR_BADCOUNT (USN_ERANGE); else return it with .status."""
+        h = DrainHdr()
+        rc = self.ctx.L.usn_rings_drain_info(self.ctx.h, C.byref(self.desc), stream, C.byref(h))
+        if strict or rc != USN_ERANGE:
+            check(rc, "usn_rings_drain_info")
+        h.status = rc
+        return h
+
+    _get = DeviceDelivery._get
+
+    def ep_off(self) -> np.ndarray:
+        """slots of id e = [ep_off[e], ep_off[e + 1]), e <= USN_MAX_ENDPOINTS"""
+        return self._get(self.desc.ep_off, np.uint32, USN_MAX_ENDPOINTS + 2)
+
+    def ep_boff(self) -> np.ndarray:
+        """bytes of id e = [ep_boff[e], ep_boff[e + 1])"""
+        return self._get(self.desc.ep_boff, np.uint64, USN_MAX_ENDPOINTS + 2)
+
+    def _ids(self, ptr) -> np.ndarray:
+        return self._get(ptr, np.uint32, USN_MAX_ENDPOINTS + 1)
+
+    def from_(self) -> np.ndarray:
+        return self._ids(self.desc.from_)
+
+    def take(self) -> np.ndarray:
+        return self._ids(self.desc.take)
+
+    def left(self) -> np.ndarray:
+        return self._ids(self.desc.left)
+
+    # the output arrays are usn_pdelivery's
+    src, lens, off16 = DevicePackedDelivery.src, DevicePackedDelivery.lens, DevicePackedDelivery.off16
+    bytes, free = DevicePackedDelivery.bytes, DevicePackedDelivery.free
