@@ -730,6 +730,107 @@ int usn_rings_drain(usn_ctx *ctx, usn_ringset *rs, usn_drain *d, void *hip_strea
  * state of a budgeted consumer. */
 int usn_rings_drain_info(usn_ctx *ctx, const usn_drain *d, void *hip_stream, usn_drain_hdr *host_out);
 
+/* ---- byte-ring delivery: persistent endpoint rings, byte-compact -------------
+ * usn_deliver_rings' lifetime with usn_deliver_packed's layout.  A byte ring
+ * set holds, per endpoint id e, a descriptor ring of D[e] entries (0 or a power
+ * of two of at most 2^30) and a byte ring of B[e] 16-byte units (0 or a power
+ * of two of at most 2^28; D and B are both zero or both not): descriptors
+ * [desc_off[e], desc_off[e+1]) of lens / src / pos16, units [unit_off[e],
+ * unit_off[e+1]) of frames.  head / tail count frames and btail counts units,
+ * all free-running in 32 bits.  pos16[q] is the free-running unit position of
+ * the first unit of the frame in descriptor q.  THERE IS NO BYTE HEAD: a
+ * consumer moves head[e] only, and the units ring e holds are 0 when head ==
+ * tail, else btail[e] - pos16[desc_off[e] + (head[e] & (D - 1))] in 32-bit
+ * arithmetic; the bytes of queued frames [h, h + t) follow from two pos16
+ * reads and are at most two contiguous spans.
+ *
+ * usn_deliver_brings offers receiver e exactly usn_deliver_round's round ring
+ * (segments k = 0 .. count - 1, the receiver rule, registered ids only).  Frame
+ * j of it has u_j = max(1, ceil16(len_j) / 16) units.  With fill = tail - head,
+ * free_d = D - min(fill, D) and free_u = B - min(used, B) (a head ahead of the
+ * tail, used > B and D = 0 all give no room), frame j is accepted iff j <
+ * free_d and the sum of u_i over i <= j is at most free_u: ONE cut, the
+ * accepted frames are a prefix, a frame never overtakes an earlier one, and
+ * nothing is consumed within a call.  Accepted frame j gets descriptor
+ * desc_off[e] + ((first[e] + j) & (D - 1)) with lens = its true length, src =
+ * its index inside its own source ring and pos16 = bfirst[e] + the sum of u_i
+ * over i < j; its unit k lies at byte 16 * (unit_off[e] + ((pos16 + k) & (B -
+ * 1))), so a frame may straddle the ring's end at any unit boundary.  Bytes
+ * [0, len) are the frame and [len, ceil16(len)) zero; nothing is truncated (no
+ * USN_DV_LONG).  first / bfirst are tail / btail before the call, acc / drop
+ * (saturating) / acc_units the receiver's accepted frames, dropped frames and
+ * accepted units, seg_acc[8e + k] segment k's accepted share.
+ *
+ * No descriptor and no byte between head and tail is written, nothing of
+ * frames, lens, src or pos16 outside the accepted frames' descriptors and units
+ * is written (staging lives in the scratch behind hdr), and a dropped frame's
+ * bytes are never read (its length is: the cut depends on it).  tail[e] +=
+ * acc[e] and btail[e] += acc_units[e] happen in the call's last launch only.
+ * Calls on one set must be stream-ordered with each other and with head
+ * updates.  Until a device drain exists a consumer ordered behind a call reads
+ * ring e as frames head .. tail - 1 through lens / src / pos16. */
+#define USN_HAS_DELIVER_BRINGS 1
+typedef struct {
+  uint64_t offered;         /* frames the round's rule gives all receivers */
+  uint64_t dropped;         /* offered - accepted */
+  uint64_t accepted_units;  /* 16-byte units appended by this call */
+  uint32_t accepted;        /* frames appended by this call */
+  uint32_t n_recv;          /* receivers with accepted > 0 */
+  uint32_t flags;           /* USN_DV_DROPPED */
+  uint32_t _r;
+} usn_bringset_hdr;
+typedef struct {
+  uint8_t  *frames;     /* total_units * 16 bytes */
+  uint16_t *lens;       /* total_desc: true lengths */
+  uint32_t *src;        /* total_desc: frame index inside the frame's own source ring */
+  uint32_t *pos16;      /* total_desc: free-running unit position of the frame's first unit */
+  uint32_t *desc_off;   /* USN_MAX_ENDPOINTS + 2: exclusive prefix of D */
+  uint32_t *unit_off;   /* USN_MAX_ENDPOINTS + 2: exclusive prefix of B */
+  uint32_t *head;       /* USN_MAX_ENDPOINTS + 1, frames, written by the consumer only */
+  uint32_t *tail;       /* USN_MAX_ENDPOINTS + 1, frames, written by the call's last launch only */
+  uint32_t *btail;      /* USN_MAX_ENDPOINTS + 1, units, written by the call's last launch only */
+  uint32_t *first;      /* per id: tail[e] before this call */
+  uint32_t *bfirst;     /* per id: btail[e] before this call */
+  uint32_t *acc;        /* per id: frames accepted by this call */
+  uint32_t *drop;       /* per id: frames dropped by this call (saturating) */
+  uint32_t *acc_units;  /* per id: units accepted by this call */
+  uint32_t *seg_acc;    /* USN_ROUND_MAX * (USN_MAX_ENDPOINTS + 1): accepted frames of segment (e, k) at [8e + k] */
+  usn_bringset_hdr *hdr;   /* followed by the kernels' scratch (plan, staging, tile sums) */
+  uint64_t total_desc, total_units;
+  uint32_t ready, _r;   /* ready: set by usn_bringset_init */
+} usn_bringset;
+/* Bytes of a byte ring set: 0 unless total_desc and total_units both lie in
+ * [1, 2^32).  usn_bringset_bind carves device (or, for layout checks, host)
+ * memory of that size into 256-byte aligned arrays and clears `ready`:
+ * USN_EINVAL for such arguments, USN_ERANGE when `bytes` is too small.  The
+ * scratch holds a staging entry per descriptor and the sums of total_desc /
+ * USN_DELIVER_TILE + USN_MAX_ENDPOINTS + 2 tiles. */
+size_t usn_bringset_bytes(uint64_t total_desc, uint64_t total_units);
+int usn_bringset_bind(void *dev_mem, size_t bytes, uint64_t total_desc, uint64_t total_units,
+                      usn_bringset *out);
+/* Lays both rings of ids below n_ids <= USN_MAX_ENDPOINTS out back to back
+ * (ids from n_ids on get none): USN_EINVAL for a size that is no power of two,
+ * a D above 2^30 or a B above 2^28, a pair of which only one is zero, or sums
+ * above the totals.  Uploads desc_off / unit_off, zeroes the counters, the
+ * per-call arrays and the header, and sets `ready`.  A setup call: it
+ * synchronises `hip_stream`. */
+int usn_bringset_init(usn_ctx *ctx, usn_bringset *rs, const uint32_t *ring_desc,
+                      const uint32_t *ring_units, uint32_t n_ids, void *hip_stream);
+/* As usn_ringset_set_head. */
+int usn_bringset_set_head(usn_ctx *ctx, usn_bringset *rs, const uint32_t *head, uint32_t n_ids,
+                          void *hip_stream);
+/* usn_deliver_rings' arguments, validation (without the slot rules), event
+ * waits, receiver table and return codes, plus USN_EINVAL for a set that is
+ * not ready.  Five launches on `hip_stream` whatever count is (plan, merge,
+ * scan, copy, commit); no host synchronisation and no copy in the steady
+ * state. */
+int usn_deliver_brings(usn_ctx *ctx, const usn_batch *b, const usn_result *r, uint32_t count,
+                       usn_bringset *rs, void *hip_stream);
+/* Synchronises `hip_stream` and copies the header to the host: USN_ERANGE
+ * when USN_DV_DROPPED is set (host_out is filled all the same). */
+int usn_deliver_brings_info(usn_ctx *ctx, const usn_bringset *rs, void *hip_stream,
+                            usn_bringset_hdr *host_out);
+
 /* Forget the carried decision cache of one endpoint (last_pkt = None). */
 int usn_cache_clear(usn_ctx *ctx, uint16_t endpoint);
 

@@ -32,8 +32,17 @@ and to ONE device-to-device copy of need_bytes, the three alternating in blocks.
 Every timed drain follows an append and every timed append a drain, each
 outside the other's timed span: the drain moves the heads itself.
 
+--brings times usn_deliver_brings (the round appended to persistent BYTE-COMPACT
+rings: five launches) next to usn_deliver_rings at --slot on the same rings and
+results and to ONE device-to-device copy of 16 x accepted_units bytes,
+alternating in blocks: once with ample rings, once with byte rings of the power
+of two nearest half of each endpoint's offered units.  Heads are reset as for
+--rings.  The sets' sizes in bytes and the spread of the ring mode's own block
+medians are recorded next to the times.
+
 usage: python tools/deliver_bench.py [--config c5] [--frames N] [--multi 2] [--rounds 2]
-                                     [--launches 120] [--slot 64] [--packed | --round | --rings | --drain]
+                                     [--launches 120] [--slot 64]
+                                     [--packed | --round | --rings | --drain | --brings]
                                      [--json out.json]
 """
 import argparse
@@ -62,6 +71,7 @@ def main():
     ap.add_argument("--round", action="store_true")
     ap.add_argument("--rings", action="store_true")
     ap.add_argument("--drain", action="store_true")
+    ap.add_argument("--brings", action="store_true")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     n, Q, R = a.frames, a.multi, a.rounds
@@ -152,6 +162,8 @@ def main():
         return rings_mode(a, ctx, s, hip, bs, rs, need, timed, block)
     if a.drain:
         return drain_mode(a, ctx, s, hip, bs, rs, need, timed, block)
+    if a.brings:
+        return brings_mode(a, ctx, s, hip, bs, rs, need, timed, block)
     dl_us, cp_us = [], []
     while len(dl_us) < a.launches:
         dl_us += timed(deliver, block)
@@ -362,6 +374,98 @@ def drain_mode(a, ctx, s, hip, bs, rs, need, timed, block):
     out["drain_over_copy"] = round(out["drain_us"] / out["d2d_copy_us"], 2)
     out["append_over_copy"] = round(out["append_us"] / out["d2d_copy_us"], 2)
     out["drain_over_append"] = round(out["drain_us"] / out["append_us"], 3)
+    print(json.dumps(out), flush=True)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+    ctx.close()
+
+
+def brings_mode(a, ctx, s, hip, bs, rs, need, timed, block):
+    """usn_deliver_brings (ample rings, then byte rings of about half the offered units) against
+    usn_deliver_rings at --slot and one copy of the accepted units"""
+    n, Q, R = a.frames, a.multi, a.rounds
+    rd = lib.DeviceRoundDelivery(ctx, n * Q, a.slot)
+    ctx.deliver_round(bs[0], rs[0], rd, s)
+    assert rd.info(s).need == need
+    off = rd.ep_off().astype(np.int64)
+    cnt = np.diff(off, append=need)                            # frames a call offers each endpoint
+    u = np.maximum(1, (rd.lens(0, need).astype(np.int64) + 15) // 16)
+    csum = np.concatenate([[0], np.cumsum(u)])
+    units = csum[np.minimum(off + cnt, need)] - csum[np.minimum(off, need)]   # ... and units
+    rd.free()
+    ids = int(np.flatnonzero(cnt)[-1]) + 1
+    cnt, units = cnt[:ids], units[:ids]
+    pow2 = lambda v: np.where(v > 0, 2 ** np.ceil(np.log2(np.maximum(v, 1))), 0).astype(np.uint32)
+    D, B = pow2(cnt), pow2(units)
+    Bh = pow2(np.where(units > 0, np.maximum(units / 2 ** 1.5, 1), 0))   # the power of two nearest units / 2
+    sets = {"brings": [lib.DeviceBRingSet(ctx, D, B) for _ in range(R)],
+            "brings_half": [lib.DeviceBRingSet(ctx, D, Bh) for _ in range(R)],
+            "rings": [lib.DeviceRingSet(ctx, D, a.slot) for _ in range(R)]}
+    total_u = int(units.sum())
+    cp_src, cp_dst = ctx.alloc(16 * total_u), ctx.alloc(16 * total_u)
+
+    def call(name):
+        f = ctx.deliver_rings if name == "rings" else ctx.deliver_brings
+        return lambda r: f(bs[r], rs[r], sets[name][r], s)
+
+    def drain(name):   # head = tail on the stream, outside the timed span
+        def f(r):
+            d = sets[name][r].desc
+            assert hip.hipMemcpyDtoDAsync(d.head, d.tail, 4 * (lib.USN_MAX_ENDPOINTS + 1), s) == 0
+        return f
+
+    def copy(nu):
+        return lambda r: hip.hipMemcpyDtoDAsync(cp_dst.ptr, cp_src.ptr, 16 * nu, s)
+
+    # the first append (heads 0): the headers, and the smallest ring against the ring mode's
+    hdrs = {}
+    for name in sets:
+        call(name)(0)
+        hdrs[name] = sets[name][0].info(s, strict=False)
+    hb = hdrs["brings"]
+    assert (hb.accepted, hb.accepted_units, hb.flags) == (need, total_u, 0), "the ample byte rings dropped"
+    assert (hdrs["rings"].accepted, hdrs["rings"].flags) == (need, 0), "the ample rings dropped or truncated"
+    e = int(np.argmin(np.where(cnt > 0, cnt, cnt.max() + 1)))
+    lens, src, slots = sets["rings"][0].ring(e)
+    blens, bsrc, body = sets["brings"][0].ring(e)
+    assert np.array_equal(blens, lens) and np.array_equal(bsrc, src), "ring %d differs from the ring mode's" % e
+    assert all(np.array_equal(b, row[:b.size]) for b, row in zip(body, slots)), "ring %d: bytes differ" % e
+    acc_half, units_half = int(hdrs["brings_half"].accepted), int(hdrs["brings_half"].accepted_units)
+    for name in sets:
+        for r in list(range(R)) * 2:   # warm-up
+            drain(name)(r)
+            call(name)(r)
+        for r in range(R):
+            drain(name)(r)
+    us = {k: [] for k in ("brings", "rings", "d2d_copy", "brings_half", "d2d_copy_half")}
+    while len(us["brings"]) < a.launches:
+        us["brings"] += timed(call("brings"), block, after=drain("brings"))
+        us["rings"] += timed(call("rings"), block, after=drain("rings"))
+        us["d2d_copy"] += timed(copy(total_u), block)
+        us["brings_half"] += timed(call("brings_half"), block, after=drain("brings_half"))
+        us["d2d_copy_half"] += timed(copy(units_half), block)
+    for r in range(R):   # the last timed calls: nothing dropped from the ample rings, the same share from the others
+        assert sets["brings"][r].info(s).accepted_units == total_u
+        assert sets["brings_half"][r].info(s, strict=False).accepted_units == units_half
+    blocks = [statistics.median(us["rings"][i:i + block]) for i in range(0, len(us["rings"]), block)]
+    out = dict(config=a.config, frames_per_call=n * Q, rings=Q, slot=a.slot, offered_frames=need,
+               offered_units=total_u, bytes_per_offered_frame=round(16 * total_u / max(need, 1), 1),
+               endpoints_with_a_ring=int((D > 0).sum()), descriptors=int(D.sum()), units_ample=int(B.sum()),
+               units_half=int(Bh.sum()), accepted_half=acc_half, accepted_units_half=units_half,
+               dropped_share_half=round(1 - acc_half / max(need, 1), 3),
+               bringset_bytes=int(sets["brings"][0].nbytes), bringset_half_bytes=int(sets["brings_half"][0].nbytes),
+               ringset_bytes=int(ctx.L.usn_ringset_bytes(max(int(D.sum()), 1), a.slot)),
+               launches=len(us["brings"]), launches_per_call_brings=5, launches_per_call_rings=3,
+               rings_block_medians_us=[round(b, 1) for b in blocks],
+               rings_block_p10_us=round(float(np.percentile(blocks, 10)), 1),
+               rings_block_p90_us=round(float(np.percentile(blocks, 90)), 1))
+    out["footprint_ratio"] = round(out["ringset_bytes"] / out["bringset_bytes"], 2)
+    for k, v in us.items():
+        out.update(stats(v, k))
+    out["brings_over_rings"] = round(out["brings_us"] / out["rings_us"], 3)
+    out["brings_over_copy"] = round(out["brings_us"] / out["d2d_copy_us"], 2)
+    out["brings_half_over_copy"] = round(out["brings_half_us"] / out["d2d_copy_half_us"], 2)
     print(json.dumps(out), flush=True)
     if a.json:
         with open(a.json, "w") as fh:

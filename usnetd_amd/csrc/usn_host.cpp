@@ -4147,6 +4147,189 @@ int usn_deliver_rings_info(usn_ctx *c, const usn_ringset *rs, void *stream, usn_
   return out->flags & (USN_DV_DROPPED | USN_DV_LONG) ? USN_ERANGE : USN_OK;
 }
 
+/* ---- byte-ring delivery: persistent byte-compact rings (usn_deliver_brings.hip) */
+struct BRingSetLayout {
+  size_t frames, lens, src, pos16, desc_off, unit_off, head, tail, btail, first, bfirst, acc, drop, acc_units,
+      seg_acc, hdr, total;
+};
+static bool bringset_layout(uint64_t desc, uint64_t units, BRingSetLayout &L) {
+  if (desc == 0 || desc > 0xFFFFFFFFull || units == 0 || units > 0xFFFFFFFFull) return false;
+  const size_t ids = (size_t)USN_DT_IDS * 4;
+  size_t off = 0;
+  L.frames = off; off = align256(off + (size_t)units * 16);
+  L.lens = off; off = align256(off + (size_t)desc * 2);
+  L.src = off; off = align256(off + (size_t)desc * 4);
+  L.pos16 = off; off = align256(off + (size_t)desc * 4);
+  L.desc_off = off; off = align256(off + ids + 4);
+  L.unit_off = off; off = align256(off + ids + 4);
+  L.head = off; off = align256(off + ids);
+  L.tail = off; off = align256(off + ids);
+  L.btail = off; off = align256(off + ids);
+  L.first = off; off = align256(off + ids);
+  L.bfirst = off; off = align256(off + ids);
+  L.acc = off; off = align256(off + ids);
+  L.drop = off; off = align256(off + ids);
+  L.acc_units = off; off = align256(off + ids);
+  L.seg_acc = off; off = align256(off + ids * USN_ROUND_MAX);
+  L.hdr = off; off = align256(off + usn::DELIVER_SCRATCH_OFF + usn::brings_scratch_bytes(desc));
+  L.total = off;
+  return true;
+}
+
+size_t usn_bringset_bytes(uint64_t total_desc, uint64_t total_units) {
+  BRingSetLayout L;
+  return bringset_layout(total_desc, total_units, L) ? L.total : 0;
+}
+
+int usn_bringset_bind(void *mem, size_t bytes, uint64_t total_desc, uint64_t total_units, usn_bringset *out) {
+  BRingSetLayout L;
+  if (!mem || !out || ((uintptr_t)mem & 15) != 0 || !bringset_layout(total_desc, total_units, L)) return USN_EINVAL;
+  if (bytes < L.total) return USN_ERANGE;
+  uint8_t *b = static_cast<uint8_t *>(mem);
+  auto u32 = [b](size_t off) { return reinterpret_cast<uint32_t *>(b + off); };
+  out->frames = b + L.frames;
+  out->lens = reinterpret_cast<uint16_t *>(b + L.lens);
+  out->src = u32(L.src);
+  out->pos16 = u32(L.pos16);
+  out->desc_off = u32(L.desc_off);
+  out->unit_off = u32(L.unit_off);
+  out->head = u32(L.head);
+  out->tail = u32(L.tail);
+  out->btail = u32(L.btail);
+  out->first = u32(L.first);
+  out->bfirst = u32(L.bfirst);
+  out->acc = u32(L.acc);
+  out->drop = u32(L.drop);
+  out->acc_units = u32(L.acc_units);
+  out->seg_acc = u32(L.seg_acc);
+  out->hdr = reinterpret_cast<usn_bringset_hdr *>(b + L.hdr);
+  out->total_desc = total_desc;
+  out->total_units = total_units;
+  out->ready = 0;
+  out->_r = 0;
+  return USN_OK;
+}
+
+/* what the byte-ring entry points ask of a bound set */
+static bool bringset_ok(const usn_bringset *rs) {
+  if (!rs->frames || !rs->lens || !rs->src || !rs->pos16 || !rs->desc_off || !rs->unit_off || !rs->head ||
+      !rs->tail || !rs->btail || !rs->first || !rs->bfirst || !rs->acc || !rs->drop || !rs->acc_units ||
+      !rs->seg_acc || !rs->hdr)
+    return false;
+  if (rs->total_desc == 0 || rs->total_desc > 0xFFFFFFFFull || rs->total_units == 0 ||
+      rs->total_units > 0xFFFFFFFFull)
+    return false;
+  const uintptr_t vec = (uintptr_t)rs->frames | (uintptr_t)rs->desc_off | (uintptr_t)rs->unit_off |
+                        (uintptr_t)rs->head | (uintptr_t)rs->tail | (uintptr_t)rs->btail |
+                        (uintptr_t)rs->first | (uintptr_t)rs->bfirst | (uintptr_t)rs->acc | (uintptr_t)rs->drop |
+                        (uintptr_t)rs->acc_units | (uintptr_t)rs->seg_acc | (uintptr_t)rs->hdr;
+  return (vec & 15) == 0;   // the kernels' 16-byte loads and stores
+}
+
+int usn_bringset_init(usn_ctx *c, usn_bringset *rs, const uint32_t *ring_desc, const uint32_t *ring_units,
+                      uint32_t n_ids, void *stream) {
+  if (!c || !rs || !bringset_ok(rs) || ((!ring_desc || !ring_units) && n_ids) || n_ids > USN_MAX_ENDPOINTS)
+    return USN_EINVAL;
+  std::vector<uint32_t> doff(USN_DT_IDS + 1, 0u), uoff(USN_DT_IDS + 1, 0u);
+  uint64_t dsum = 0, usum = 0;
+  for (uint32_t e = 0; e < USN_DT_IDS; ++e) {
+    const uint32_t D = e < n_ids ? ring_desc[e] : 0u, B = e < n_ids ? ring_units[e] : 0u;
+    if ((D & (D - 1)) != 0 || D > (1u << 30) || (B & (B - 1)) != 0 || B > (1u << 28) || !D != !B) return USN_EINVAL;
+    doff[e] = (uint32_t)dsum;
+    uoff[e] = (uint32_t)usum;
+    dsum += D;
+    usum += B;
+    if (dsum > rs->total_desc || usum > rs->total_units) return USN_EINVAL;
+  }
+  doff[USN_DT_IDS] = (uint32_t)dsum;
+  uoff[USN_DT_IDS] = (uint32_t)usum;
+  if (c->device < 0) return USN_ENODEV;
+  rs->ready = 0;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  /* head .. seg_acc and the header with the per-id scratch lie behind unit_off in one piece */
+  uint8_t *zero = reinterpret_cast<uint8_t *>(rs->head);
+  const size_t zbytes = (size_t)(reinterpret_cast<uint8_t *>(rs->hdr) - zero) + usn::DELIVER_SCRATCH_OFF +
+                        usn::BRINGS_IDS_BYTES;
+  HIPCHK(hipMemsetAsync(zero, 0, zbytes, st));
+  HIPCHK(hipMemcpyAsync(rs->desc_off, doff.data(), doff.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(rs->unit_off, uoff.data(), uoff.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  rs->ready = 1;
+  return USN_OK;
+}
+
+int usn_bringset_set_head(usn_ctx *c, usn_bringset *rs, const uint32_t *head, uint32_t n_ids, void *stream) {
+  if (!c || !rs || !rs->head || !head || n_ids > USN_MAX_ENDPOINTS) return USN_EINVAL;
+  if (c->device < 0) return USN_ENODEV;
+  if (!rs->ready) return USN_EINVAL;
+  if (n_ids == 0) return USN_OK;
+  HIPCHK(hipMemcpyAsync(rs->head, head, (size_t)n_ids * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));   // the caller's array may be reused
+  return USN_OK;
+}
+
+int usn_deliver_brings(usn_ctx *c, const usn_batch *b, const usn_result *r, uint32_t count,
+                       usn_bringset *rs, void *stream) {
+  if (!c || !b || !r || !rs || count == 0 || count > USN_ROUND_MAX) return USN_EINVAL;
+  if (!bringset_ok(rs) || !rs->ready) return USN_EINVAL;
+  for (uint32_t k = 0; k < count; ++k)
+    if (!deliver_inputs_ok(&b[k], &r[k])) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  std::lock_guard<std::mutex> g(c->mu);
+  usn::BRingsDeliverArgs a;
+  std::memset(&a, 0, sizeof a);
+  Replica *Rp = nullptr;
+  { int s = round_rings(c, b, r, count, stream, &Rp, a); if (s) return s; }
+  Replica &R = *Rp;
+  a.out_frames = rs->frames;
+  a.out_lens = rs->lens;
+  a.out_src = rs->src;
+  a.out_pos16 = rs->pos16;
+  a.desc_off = rs->desc_off;
+  a.unit_off = rs->unit_off;
+  a.head = rs->head;
+  a.tail = rs->tail;
+  a.btail = rs->btail;
+  a.first = rs->first;
+  a.bfirst = rs->bfirst;
+  a.acc = rs->acc;
+  a.drop = rs->drop;
+  a.acc_units = rs->acc_units;
+  a.seg_acc = rs->seg_acc;
+  a.hdr = rs->hdr;
+  /* the scratch, in brings_scratch_bytes' order; every piece a multiple of 16 bytes */
+  uint8_t *p = reinterpret_cast<uint8_t *>(rs->hdr) + usn::DELIVER_SCRATCH_OFF;
+  auto take = [&p](size_t bytes) { uint8_t *q = p; p += (bytes + 15) & ~(size_t)15; return q; };
+  const size_t ids = (size_t)USN_DT_IDS * 4, nt = usn::brings_max_tiles(rs->total_desc);
+  a.tile_pfx = reinterpret_cast<uint32_t *>(take(ids));
+  a.free_u = reinterpret_cast<uint32_t *>(take(ids));
+  a.run_acc = reinterpret_cast<uint32_t *>(take(ids));
+  a.run_units = reinterpret_cast<uint32_t *>(take(ids));
+  a.seg_d = reinterpret_cast<uint32_t *>(take(ids * USN_ROUND_MAX));
+  a.offered = reinterpret_cast<uint64_t *>(take(ids * 2));
+  a.st_src = reinterpret_cast<uint32_t *>(take((size_t)rs->total_desc * 4));
+  a.st_lens = reinterpret_cast<uint16_t *>(take((size_t)rs->total_desc * 2));
+  a.tile_u = reinterpret_cast<uint32_t *>(take(nt * 4));
+  a.tile_first = reinterpret_cast<uint32_t *>(take(nt * 4));
+  a.tile_base = reinterpret_cast<uint32_t *>(take(nt * 4));
+  a.total_desc = (uint32_t)rs->total_desc;
+  a.total_units = (uint32_t)rs->total_units;
+  a.max_tiles = (uint32_t)std::min<size_t>(nt, 0xFFFFFFFFu);
+  // usn_deliver's pack grid: what the device holds at once
+  HIPCHK(usn::launch_deliver_brings(a, (uint32_t)std::max(R.n_cu, 1) * 8u, (hipStream_t)stream));
+  if (c->sel < c->reps.size() && c->reps[c->sel].device != R.device) HIPCHK(hipSetDevice(c->device));
+  return USN_OK;
+}
+
+int usn_deliver_brings_info(usn_ctx *c, const usn_bringset *rs, void *stream, usn_bringset_hdr *out) {
+  if (!c || !rs || !rs->hdr || !out) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  HIPCHK(hipMemcpy(out, rs->hdr, sizeof *out, hipMemcpyDeviceToHost));
+  return out->flags & USN_DV_DROPPED ? USN_ERANGE : USN_OK;
+}
+
 /* ---- ring drain: the consumer of a ring set (usn_rings_drain.hip) ----------- */
 struct DrainLayout {
   size_t frames, off16, lens, src, ep_off, ep_boff, budget, from, take, left, hdr, total;

@@ -452,6 +452,78 @@ constexpr size_t drain_scratch_bytes(uint64_t cap) {
 }
 hipError_t launch_rings_drain(const DrainArgs &a, uint32_t grid, hipStream_t stream);
 
+/* ---- byte-ring delivery (usn_deliver_brings.hip): a poll round appended to
+ * the persistent, byte-compact rings of a usn_bringset.  Five launches,
+ * whatever count is:
+ *   brings_plan_kernel    one workgroup: the ring plan's counting, the id's
+ *                         free descriptors and free units (head, tail, btail
+ *                         and pos16 at the head descriptor), the descriptor-
+ *                         bounded acceptance per segment (seg_d), first /
+ *                         bfirst, the offered count per id and the tile prefix
+ *                         over the descriptor-bounded runs
+ *   brings_merge_kernel   device-sized grid: the ring pack's segment cuts and
+ *                         merge per tile; src / lens into the staging area,
+ *                         the tile's units into tile_u[t]; no frame byte moves
+ *   brings_scan_kernel    one workgroup: exclusive scan of tile_u restarted at
+ *                         every receiver's first tile (tile_base)
+ *   brings_copy_kernel    device-sized grid: a tile behind the byte cut leaves
+ *                         at once; else the units' scan in LDS, the cut at
+ *                         free_u, the descriptors, the output-stationary gather
+ *                         into the wrapped byte ring, and one tile per run
+ *                         notes the run's accepted frames and units
+ *   brings_commit_kernel  one workgroup: acc, drop, acc_units, seg_acc, the
+ *                         header, tail and btail
+ * The per-ring fields are RoundDeliverArgs'. */
+struct BRingsDeliverArgs {
+  const uint8_t *frames[USN_ROUND_MAX];
+  uint64_t stride[USN_ROUND_MAX];
+  const uint64_t *offsets[USN_ROUND_MAX];
+  const uint16_t *lens[USN_ROUND_MAX];
+  const uint32_t *index[USN_ROUND_MAX];
+  const uint32_t *bin_off[USN_ROUND_MAX];
+  const usn_summary *summary[USN_ROUND_MAX];
+  uint32_t n[USN_ROUND_MAX];
+  uint32_t src[USN_ROUND_MAX];
+  const uint16_t *eptab;     /* as DeliverArgs */
+  uint8_t *out_frames;       /* the set's arrays: total_units units, total_desc descriptors */
+  uint16_t *out_lens;
+  uint32_t *out_src;
+  uint32_t *out_pos16;
+  const uint32_t *desc_off;  /* [USN_DT_IDS + 1] */
+  const uint32_t *unit_off;  /* [USN_DT_IDS + 1] */
+  const uint32_t *head;      /* [USN_DT_IDS] */
+  uint32_t *tail, *btail;    /* [USN_DT_IDS]: read by the plan, moved by the commit */
+  uint32_t *first, *bfirst, *acc, *drop, *acc_units;   /* [USN_DT_IDS] each */
+  uint32_t *seg_acc;         /* [USN_ROUND_MAX * USN_DT_IDS] */
+  usn_bringset_hdr *hdr;
+  /* scratch */
+  uint32_t *tile_pfx;        /* [USN_DT_IDS]: tiles of the descriptor-bounded runs of the ids below */
+  uint32_t *free_u;          /* [USN_DT_IDS]: free units before the call */
+  uint32_t *run_acc;         /* [USN_DT_IDS]: a run's accepted frames, by its one deciding tile */
+  uint32_t *run_units;       /* [USN_DT_IDS]: ... and units */
+  uint32_t *seg_d;           /* [USN_ROUND_MAX * USN_DT_IDS]: segment (e, k)'s share of the first free_d frames */
+  uint64_t *offered;         /* [USN_DT_IDS]: frames offered to the id */
+  uint32_t *st_src;          /* [total_desc]: the run of id e at desc_off[e], unwrapped */
+  uint16_t *st_lens;         /* [total_desc] */
+  uint32_t *tile_u;          /* [max_tiles]: units of tile t */
+  uint32_t *tile_first;      /* [max_tiles]: first tile of t's run */
+  uint32_t *tile_base;       /* [max_tiles]: units before tile t in its run (saturating) */
+  uint32_t total_desc, total_units, max_tiles;
+};
+/* the most tiles a call has: a receiver's last tile may be short */
+constexpr size_t brings_max_tiles(uint64_t total_desc) {
+  return (size_t)(total_desc / USN_DELIVER_TILE) + USN_DT_IDS + 1;
+}
+/* scratch behind usn_bringset.hdr, from DELIVER_SCRATCH_OFF: the per-id part
+ * (tile_pfx, free_u, run_acc, run_units, seg_d, offered), then st_src, st_lens
+ * (each rounded up to 16 bytes) and tile_u, tile_first, tile_base */
+constexpr size_t BRINGS_IDS_BYTES = (size_t)USN_DT_IDS * (4 * 4 + 4 * USN_ROUND_MAX + 8);
+constexpr size_t brings_scratch_bytes(uint64_t total_desc) {
+  return BRINGS_IDS_BYTES + (((size_t)total_desc * 4 + 15) & ~(size_t)15) +
+         (((size_t)total_desc * 2 + 15) & ~(size_t)15) + 3 * ((brings_max_tiles(total_desc) * 4 + 15) & ~(size_t)15);
+}
+hipError_t launch_deliver_brings(const BRingsDeliverArgs &a, uint32_t grid, hipStream_t stream);
+
 }  // namespace usn
 
 /* the same kernels at 512 threads per tile (a second compilation of

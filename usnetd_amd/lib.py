@@ -28,6 +28,7 @@ USN_DELIVER_TILE = 512   # output slots per pack tile of usn_deliver (usn_classi
 DV_OVERFLOW, DV_LONG = 1, 2
 DV_OVERFLOW_BYTES = 4   # usn_deliver_packed: need_bytes > cap_bytes
 DV_DROPPED = 8          # usn_deliver_rings: an offered frame found its ring full
+HAS_DELIVER_BRINGS = 1  # USN_HAS_DELIVER_BRINGS: the byte-compact persistent rings (usn_deliver_brings)
 DR_MORE = 16            # usn_rings_drain: a ring keeps queued frames after the call
 DR_BADCOUNT = 32        # usn_rings_drain: a ring's tail - head exceeds its size (not drained)
 R_WINDOW = 7
@@ -118,6 +119,20 @@ class RingSet(C.Structure):
                 ("first", C.c_void_p), ("acc", C.c_void_p), ("drop", C.c_void_p),
                 ("seg_acc", C.c_void_p), ("hdr", C.c_void_p), ("total", C.c_uint64),
                 ("slot", C.c_uint32), ("ready", C.c_uint32)]
+
+
+class BRingSetHdr(C.Structure):
+    _fields_ = [("offered", C.c_uint64), ("dropped", C.c_uint64), ("accepted_units", C.c_uint64),
+                ("accepted", C.c_uint32), ("n_recv", C.c_uint32), ("flags", C.c_uint32),
+                ("_r", C.c_uint32)]
+
+
+class BRingSet(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ("frames", "lens", "src", "pos16", "desc_off", "unit_off",
+                                          "head", "tail", "btail", "first", "bfirst", "acc", "drop",
+                                          "acc_units", "seg_acc", "hdr")] + \
+               [("total_desc", C.c_uint64), ("total_units", C.c_uint64), ("ready", C.c_uint32),
+                ("_r", C.c_uint32)]
 
 
 class DrainHdr(C.Structure):
@@ -218,6 +233,12 @@ def load(path: str | None = None):
         "usn_drain_set_budget": ([P, C.POINTER(Drain), P, U32, P], I),
         "usn_rings_drain": ([P, C.POINTER(RingSet), C.POINTER(Drain), P], I),
         "usn_rings_drain_info": ([P, C.POINTER(Drain), P, C.POINTER(DrainHdr)], I),
+        "usn_bringset_bytes": ([U64, U64], SZ),
+        "usn_bringset_bind": ([P, SZ, U64, U64, C.POINTER(BRingSet)], I),
+        "usn_bringset_init": ([P, C.POINTER(BRingSet), P, P, U32, P], I),
+        "usn_bringset_set_head": ([P, C.POINTER(BRingSet), P, U32, P], I),
+        "usn_deliver_brings": ([P, P, P, U32, C.POINTER(BRingSet), P], I),
+        "usn_deliver_brings_info": ([P, C.POINTER(BRingSet), P, C.POINTER(BRingSetHdr)], I),
     }
     optional = {"usn_set_frame_reader", "usn_ctx_create_group", "usn_ctx_replicas",
                 "usn_replica_select", "usn_replica_device", "usn_result_bytes_ep",
@@ -228,7 +249,9 @@ def load(path: str | None = None):
                 "usn_deliver_round_info", "usn_ringset_bytes", "usn_ringset_bind", "usn_ringset_init",
                 "usn_ringset_set_head", "usn_deliver_rings",
                 "usn_deliver_rings_info", "usn_drain_bytes", "usn_drain_bind", "usn_drain_set_budget",
-                "usn_rings_drain", "usn_rings_drain_info"}   # A/B builds of older ABI versions lack these
+                "usn_rings_drain", "usn_rings_drain_info", "usn_bringset_bytes", "usn_bringset_bind",
+                "usn_bringset_init", "usn_bringset_set_head", "usn_deliver_brings",
+                "usn_deliver_brings_info"}   # A/B builds of older ABI versions lack these
     for name, (args, res) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -256,7 +279,9 @@ EXPORTED = ["usn_abi_version", "usn_strerror", "usn_last_hip_error", "usn_ctx_cr
             "usn_rdelivery_bind", "usn_deliver_round", "usn_deliver_round_info",
             "usn_ringset_bytes", "usn_ringset_bind", "usn_ringset_init", "usn_ringset_set_head",
             "usn_deliver_rings", "usn_deliver_rings_info", "usn_drain_bytes", "usn_drain_bind",
-            "usn_drain_set_budget", "usn_rings_drain", "usn_rings_drain_info"]
+            "usn_drain_set_budget", "usn_rings_drain", "usn_rings_drain_info", "usn_bringset_bytes",
+            "usn_bringset_bind", "usn_bringset_init", "usn_bringset_set_head", "usn_deliver_brings",
+            "usn_deliver_brings_info"]
 
 
 def check(rc, what=""):
@@ -540,6 +565,17 @@ class Ctx:
         ra = (Result * n)(*[r.desc for r in results])
         check(self.L.usn_deliver_rings(self.h, C.cast(ba, C.c_void_p), C.cast(ra, C.c_void_p), n,
                                        C.byref(rs.desc), stream), "usn_deliver_rings")
+
+    def deliver_brings(self, batches, results, rs: "DeviceBRingSet", stream=None):
+        """Append a poll round to the persistent byte-compact rings of `rs`
+        (usn_deliver_brings): deliver_rings' round and order; a receiver takes
+        frames while a descriptor and the frame's 16-byte units are free and
+        drops the rest of its round, tail and btail move last."""
+        n = len(batches)
+        ba = (Batch * n)(*[b.desc for b in batches])
+        ra = (Result * n)(*[r.desc for r in results])
+        check(self.L.usn_deliver_brings(self.h, C.cast(ba, C.c_void_p), C.cast(ra, C.c_void_p), n,
+                                        C.byref(rs.desc), stream), "usn_deliver_brings")
 
     def drain_rings(self, rs: "DeviceRingSet", dr: "DeviceDrain", stream=None):
         """Take up to dr's budgets of the oldest queued frames of every ring of
@@ -849,6 +885,126 @@ class DeviceRingSet:
         h, t = int(self.head()[e]), int(self.tail()[e])
         pos = (h + np.arange(min((t - h) & 0xFFFFFFFF, k1 - k0), dtype=np.int64)) & (k1 - k0 - 1)
         return self.lens(k0, k1)[pos], self.src(k0, k1)[pos], self.slots(k0, k1)[pos]
+
+    def free(self):
+        if self.buf is not None:
+            self.buf.free()
+            self.buf = None
+
+
+class DeviceBRingSet:
+    """One usn_bringset: per endpoint id e a descriptor ring of ring_desc[e]
+    entries and a byte ring of ring_units[e] 16-byte units (each 0 or a power of
+    two, both or neither), free-running head / tail / btail.  `poison` fills
+    the whole allocation before usn_bringset_init."""
+
+    def __init__(self, ctx: Ctx, ring_desc, ring_units, poison: int | None = None):
+        self.ctx = ctx
+        D = np.ascontiguousarray(ring_desc, dtype=np.uint32)
+        B = np.ascontiguousarray(ring_units, dtype=np.uint32)
+        assert D.size == B.size
+        self.total_desc = max(int(D.astype(np.int64).sum()), 1)
+        self.total_units = max(int(B.astype(np.int64).sum()), 1)
+        self.nbytes = ctx.L.usn_bringset_bytes(self.total_desc, self.total_units)
+        if self.nbytes == 0:
+            raise UsnError("usn_bringset_bytes: bad totals %d, %d" % (self.total_desc, self.total_units))
+        self.buf = ctx.alloc(self.nbytes)
+        self.desc = BRingSet()
+        check(ctx.L.usn_bringset_bind(self.buf.ptr, self.nbytes, self.total_desc, self.total_units,
+                                      C.byref(self.desc)), "usn_bringset_bind")
+        if poison is not None:
+            check(ctx.L.usn_memset_d(ctx.h, self.buf.ptr, poison, self.nbytes, None), "usn_memset_d")
+            ctx.sync()
+        check(ctx.L.usn_bringset_init(ctx.h, C.byref(self.desc), D.ctypes.data, B.ctypes.data, D.size, None),
+              "usn_bringset_init")
+        self.doff = np.concatenate([[0], np.cumsum(D.astype(np.int64))])   # descriptors of e: [doff[e], doff[e + 1])
+        self.uoff = np.concatenate([[0], np.cumsum(B.astype(np.int64))])   # units of e: [uoff[e], uoff[e + 1])
+
+    def set_head(self, head, stream=None):
+        """absolute head counters of ids 0 .. len(head) - 1 (usn_bringset_set_head)"""
+        head = np.ascontiguousarray(head, dtype=np.uint32)
+        check(self.ctx.L.usn_bringset_set_head(self.ctx.h, C.byref(self.desc), head.ctypes.data,
+                                               head.size, stream), "usn_bringset_set_head")
+
+    def set_counters(self, head, tail, btail):
+        """head, tail and btail of ids 0 .. len - 1 by a plain device copy (tests and tools)"""
+        for ptr, v in ((self.desc.head, head), (self.desc.tail, tail), (self.desc.btail, btail)):
+            self.buf.upload(np.ascontiguousarray(v, dtype=np.uint32), offset=ptr - self.buf.ptr)
+
+    def info(self, stream=None, strict=True) -> BRingSetHdr:
+        """The header after the call on `stream` finished.  strict: raise on
+        USN_DV_DROPPED (USN_ERANGE); else return it with .status."""
+        h = BRingSetHdr()
+        rc = self.ctx.L.usn_deliver_brings_info(self.ctx.h, C.byref(self.desc), stream, C.byref(h))
+        if strict or rc != USN_ERANGE:
+            check(rc, "usn_deliver_brings_info")
+        h.status = rc
+        return h
+
+    _get = DeviceDelivery._get
+
+    def _ids(self, ptr) -> np.ndarray:
+        return self._get(ptr, np.uint32, USN_MAX_ENDPOINTS + 1)
+
+    def head(self) -> np.ndarray:
+        return self._ids(self.desc.head)
+
+    def tail(self) -> np.ndarray:
+        return self._ids(self.desc.tail)
+
+    def btail(self) -> np.ndarray:
+        return self._ids(self.desc.btail)
+
+    def first(self) -> np.ndarray:
+        return self._ids(self.desc.first)
+
+    def bfirst(self) -> np.ndarray:
+        return self._ids(self.desc.bfirst)
+
+    def acc(self) -> np.ndarray:
+        return self._ids(self.desc.acc)
+
+    def drop(self) -> np.ndarray:
+        return self._ids(self.desc.drop)
+
+    def acc_units(self) -> np.ndarray:
+        return self._ids(self.desc.acc_units)
+
+    def seg_acc(self) -> np.ndarray:
+        """[id, ring]: accepted frames of segment (e, k) in the last call"""
+        return self._get(self.desc.seg_acc, np.uint32,
+                         USN_ROUND_MAX * (USN_MAX_ENDPOINTS + 1)).reshape(-1, USN_ROUND_MAX)
+
+    def desc_off(self) -> np.ndarray:
+        return self._get(self.desc.desc_off, np.uint32, USN_MAX_ENDPOINTS + 2)
+
+    def unit_off(self) -> np.ndarray:
+        return self._get(self.desc.unit_off, np.uint32, USN_MAX_ENDPOINTS + 2)
+
+    def lens(self) -> np.ndarray:
+        return self._get(self.desc.lens, np.uint16, self.total_desc)
+
+    def src(self) -> np.ndarray:
+        return self._get(self.desc.src, np.uint32, self.total_desc)
+
+    def pos16(self) -> np.ndarray:
+        return self._get(self.desc.pos16, np.uint32, self.total_desc)
+
+    def units(self) -> np.ndarray:
+        """all of frames, as [total_units, 16]"""
+        return self._get(self.desc.frames, np.uint8, self.total_units * 16).reshape(-1, 16)
+
+    def ring(self, e: int):
+        """(lens, src_idx, [bytes of ceil16(len) per frame]) of ring e from head to
+        tail, in consumer order, both rings unwrapped"""
+        d0, D = int(self.doff[e]), int(self.doff[e + 1] - self.doff[e])
+        u0, B = int(self.uoff[e]), int(self.uoff[e + 1] - self.uoff[e])
+        h, t = int(self.head()[e]), int(self.tail()[e])
+        q = d0 + ((h + np.arange(min((t - h) & 0xFFFFFFFF, D), dtype=np.int64)) & (D - 1))
+        lens, src, pos, units = self.lens()[q], self.src()[q], self.pos16()[q], self.units()
+        body = [units[u0 + ((int(p) + np.arange(max(1, (int(ln) + 15) // 16))) & (B - 1))].reshape(-1)
+                for p, ln in zip(pos, lens)]
+        return lens, src, body
 
     def free(self):
         if self.buf is not None:
