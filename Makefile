@@ -5,7 +5,7 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-function
 CSRC := usnetd_amd/csrc
 LIB := usnetd_amd/libusn.so
-OBJS := build/usn_device.o build/usn_device512.o build/usn_deliver.o build/usn_deliver_packed.o build/usn_deliver_round.o build/usn_deliver_rings.o build/usn_rings_drain.o build/usn_deliver_brings.o build/usn_host.o
+OBJS := build/usn_device.o build/usn_device512.o build/usn_deliver.o build/usn_deliver_packed.o build/usn_deliver_round.o build/usn_deliver_rings.o build/usn_rings_drain.o build/usn_deliver_brings.o build/usn_brings_drain.o build/usn_host.o
 
 DAEMON := usnetd_amd/bin/usnetd
 
@@ -59,6 +59,11 @@ build/usn_deliver_brings.o: $(CSRC)/usn_deliver_brings.hip $(DELIVER_HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c -o $@ $<
 
+# the byte-ring drain (usn_brings_drain): the same flags
+build/usn_brings_drain.o: $(CSRC)/usn_brings_drain.hip $(DELIVER_HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c -o $@ $<
+
 build/usn_host.o: $(CSRC)/usn_host.cpp $(CSRC)/usn_internal.h $(CSRC)/usn_kernels.h include/usn_classify.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -x hip -c -o $@ $<
@@ -73,14 +78,14 @@ build/test/usn_host.o: $(CSRC)/usn_host.cpp $(CSRC)/usn_internal.h $(CSRC)/usn_k
 	@mkdir -p build/test
 	$(HIPCC) $(HIPFLAGS) -DUSN_TEST_HOOKS=1 -x hip -c -o $@ $<
 
-$(TESTLIB): build/usn_device.o build/usn_device512.o build/usn_deliver.o build/usn_deliver_packed.o build/usn_deliver_round.o build/usn_deliver_rings.o build/usn_rings_drain.o build/usn_deliver_brings.o build/test/usn_host.o
+$(TESTLIB): build/usn_device.o build/usn_device512.o build/usn_deliver.o build/usn_deliver_packed.o build/usn_deliver_round.o build/usn_deliver_rings.o build/usn_rings_drain.o build/usn_deliver_brings.o build/usn_brings_drain.o build/test/usn_host.o
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^
 
 oracle:
 	$(MAKE) -s -C oracle
 
 # kernel resource usage (VGPR/SGPR/LDS/occupancy) for DESIGN.md
-resources: $(CSRC)/usn_device.hip $(CSRC)/usn_deliver.hip $(CSRC)/usn_deliver_packed.hip $(CSRC)/usn_deliver_round.hip $(CSRC)/usn_deliver_rings.hip $(CSRC)/usn_rings_drain.hip $(CSRC)/usn_deliver_brings.hip
+resources: $(CSRC)/usn_device.hip $(CSRC)/usn_deliver.hip $(CSRC)/usn_deliver_packed.hip $(CSRC)/usn_deliver_round.hip $(CSRC)/usn_deliver_rings.hip $(CSRC)/usn_rings_drain.hip $(CSRC)/usn_deliver_brings.hip $(CSRC)/usn_brings_drain.hip
 	for f in $^; do $(HIPCC) $(HIPFLAGS) -c -o /dev/null $$f -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E 'Function Name|VGPRs:|SGPRs:|Occupancy|LDS Size|ScratchSize'; done
 
 asm: $(CSRC)/usn_device.hip

@@ -767,8 +767,8 @@ int usn_rings_drain_info(usn_ctx *ctx, const usn_drain *d, void *hip_stream, usn
  * bytes are never read (its length is: the cut depends on it).  tail[e] +=
  * acc[e] and btail[e] += acc_units[e] happen in the call's last launch only.
  * Calls on one set must be stream-ordered with each other and with head
- * updates.  Until a device drain exists a consumer ordered behind a call reads
- * ring e as frames head .. tail - 1 through lens / src / pos16. */
+ * updates.  usn_brings_drain (below) is the device consumer: it gathers frames
+ * head .. tail - 1 of every ring through lens / src / pos16 and moves the heads. */
 #define USN_HAS_DELIVER_BRINGS 1
 typedef struct {
   uint64_t offered;         /* frames the round's rule gives all receivers */
@@ -830,6 +830,73 @@ int usn_deliver_brings(usn_ctx *ctx, const usn_batch *b, const usn_result *r, ui
  * when USN_DV_DROPPED is set (host_out is filled all the same). */
 int usn_deliver_brings_info(usn_ctx *ctx, const usn_bringset *rs, void *hip_stream,
                             usn_bringset_hdr *host_out);
+
+/* ---- byte-ring drain: the byte rings' queued frames gathered on the device ---
+ * The consumer of a usn_bringset, into the ring drain's region: usn_drain,
+ * usn_drain_bytes, usn_drain_bind, usn_drain_set_budget and usn_drain_hdr serve
+ * both drains unchanged.  One call takes up to budget[e] frames from every
+ * ring, oldest first, lays their units back to back so that ONE copy of
+ * frames[0, need_bytes) carries the whole round to the host, and advances the
+ * heads.
+ *
+ * Per id e, with D and B the sizes of its descriptor and unit rings, h =
+ * head[e] as found, f = tail[e] - head[e] in 32-bit arithmetic, p0 = pos16 at
+ * the head descriptor desc_off[e] + (h & (D - 1)) and used = f ? btail[e] - p0
+ * : 0: avail = f when f <= D and f <= used <= B (every frame costs at least one
+ * unit, so used >= f on a sound ring), else 0.  A ring with D > 0 and f != 0
+ * that fails this has corrupt counters: it is not drained and sets
+ * USN_DR_BADCOUNT.  The selection is usn_rings_drain's: want = min(avail,
+ * budget[e]), take[e] = min(want[e], cap - min(cap, sum of want below e)),
+ * left[e] = avail - take[e] (any left > 0 sets USN_DR_MORE), from[e] = h, and
+ * ep_off is the slot prefix, ids ascending.
+ *
+ * Bytes.  p1 = btail[e] when take == avail, else pos16 at descriptor
+ * desc_off[e] + ((h + take) & (D - 1)) (a full ring taken whole has take == D,
+ * where that descriptor is the head's own: hence btail).  nu[e] = p1 - p0 in
+ * 32-bit arithmetic, 0 when take is 0; ep_boff[e+1] - ep_boff[e] = 16 * nu[e]
+ * and need_bytes = 16 * the sum of nu.  Output byte ep_boff[e] + 16 i + b is
+ * byte b of unit unit_off[e] + ((p0 + i) & (B - 1)): the ring's units are
+ * copied verbatim, pad included (zero where usn_deliver_brings wrote it).  A
+ * frame therefore occupies 16 * max(1, ceil16(len) / 16) bytes, which differs
+ * from usn_rings_drain's layout only for a zero-length frame: it keeps its one
+ * unit.  Nothing is truncated and USN_DV_LONG is never set.
+ *
+ * Descriptors.  Output slot k = ep_off[e] + j comes from descriptor q =
+ * desc_off[e] + ((h + j) & (D - 1)): lens[k] and src[k] are copied from it and
+ * off16[k] = ep_boff[e] / 16 + min(pos16[q] - p0, nu[e]).  Inconsistent
+ * descriptors are never hidden: for every selected frame the next frame's
+ * pos16 (p1 behind the last selected one) must equal its own plus max(1,
+ * ceil16(lens) / 16), and a partial take must have take <= nu <= used.  Any
+ * violation sets USN_DR_BADDESC.
+ *
+ * All or nothing.  need_bytes > cap_bytes: USN_DV_OVERFLOW_BYTES; every
+ * metadata array and need_bytes are valid and complete and no byte of `frames`
+ * is written.  USN_DR_BADDESC: what was written stays inside frames[0,
+ * min(need_bytes, cap_bytes)) and is unspecified.  In both cases NO HEAD MOVES
+ * and taken = 0.  Otherwise every byte of frames[0, need_bytes) is written,
+ * nothing past it, head[e] += take[e] and taken = selected.  frames, lens, src,
+ * pos16, tail and btail of the set are never written.
+ *
+ * The heads move in the call's LAST launch, after every unit they release has
+ * been read.  The call must still be stream-ordered with the appends
+ * (usn_deliver_brings) and head updates (usn_bringset_set_head) of the same
+ * set: the plan reads the counters in the first launch.
+ *
+ * Every index is clamped (desc_off / unit_off to the totals, take to D, nu to
+ * B, a descriptor by & (D - 1), a unit by & (B - 1), output positions to cap /
+ * cap_bytes): whatever the counters, lens or pos16 hold, no access leaves the
+ * set or the drain. */
+#define USN_HAS_BRINGS_DRAIN 1
+#define USN_BDRAIN_UTILE 4096 /* 16-byte units per copy tile of usn_brings_drain (one workgroup, four passes) */
+#define USN_DR_BADDESC 64u    /* usn_brings_drain: a selected ring's pos16 / lens chain is inconsistent: no head moved */
+/* Three launches on `hip_stream` (plan, copy, commit); no host synchronisation
+ * and no copy in the steady state.  USN_EINVAL: a null pointer, a set that is
+ * not ready, a drain that was not bound; USN_ENODEV: a USN_HOST_ONLY context. */
+int usn_brings_drain(usn_ctx *ctx, usn_bringset *rs, usn_drain *d, void *hip_stream);
+/* Synchronises `hip_stream` and copies the header to the host: USN_ERANGE when
+ * USN_DV_OVERFLOW_BYTES, USN_DR_BADCOUNT or USN_DR_BADDESC is set (host_out is
+ * filled all the same); USN_DR_MORE alone returns 0. */
+int usn_brings_drain_info(usn_ctx *ctx, const usn_drain *d, void *hip_stream, usn_drain_hdr *host_out);
 
 /* Forget the carried decision cache of one endpoint (last_pkt = None). */
 int usn_cache_clear(usn_ctx *ctx, uint16_t endpoint);

@@ -40,9 +40,15 @@ of two nearest half of each endpoint's offered units.  Heads are reset as for
 --rings.  The sets' sizes in bytes and the spread of the ring mode's own block
 medians are recorded next to the times.
 
+--bdrain times usn_brings_drain (the byte rings' consumer: three launches) with
+full budgets on --brings' ample byte rings next to ONE device-to-device copy of
+need_bytes and, where no frame is longer than --slot, to usn_rings_drain of the
+same frames out of --drain's slot rings in the same run, alternating in blocks.
+Every timed drain follows an untimed append of its own family.
+
 usage: python tools/deliver_bench.py [--config c5] [--frames N] [--multi 2] [--rounds 2]
                                      [--launches 120] [--slot 64]
-                                     [--packed | --round | --rings | --drain | --brings]
+                                     [--packed | --round | --rings | --drain | --brings | --bdrain]
                                      [--json out.json]
 """
 import argparse
@@ -72,6 +78,7 @@ def main():
     ap.add_argument("--rings", action="store_true")
     ap.add_argument("--drain", action="store_true")
     ap.add_argument("--brings", action="store_true")
+    ap.add_argument("--bdrain", action="store_true")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     n, Q, R = a.frames, a.multi, a.rounds
@@ -164,6 +171,8 @@ def main():
         return drain_mode(a, ctx, s, hip, bs, rs, need, timed, block)
     if a.brings:
         return brings_mode(a, ctx, s, hip, bs, rs, need, timed, block)
+    if a.bdrain:
+        return bdrain_mode(a, ctx, s, hip, bs, rs, need, timed, block)
     dl_us, cp_us = [], []
     while len(dl_us) < a.launches:
         dl_us += timed(deliver, block)
@@ -466,6 +475,97 @@ def brings_mode(a, ctx, s, hip, bs, rs, need, timed, block):
     out["brings_over_rings"] = round(out["brings_us"] / out["rings_us"], 3)
     out["brings_over_copy"] = round(out["brings_us"] / out["d2d_copy_us"], 2)
     out["brings_half_over_copy"] = round(out["brings_half_us"] / out["d2d_copy_half_us"], 2)
+    print(json.dumps(out), flush=True)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+    ctx.close()
+
+
+def bdrain_mode(a, ctx, s, hip, bs, rs, need, timed, block):
+    """usn_brings_drain with full budgets on ample byte rings against one copy of need_bytes and, where
+    the frames fit --slot, usn_rings_drain of the same frames out of slot rings"""
+    n, Q, R = a.frames, a.multi, a.rounds
+    rd = lib.DeviceRoundDelivery(ctx, n * Q, a.slot)
+    ctx.deliver_round(bs[0], rs[0], rd, s)
+    assert rd.info(s, strict=False).need == need
+    off = rd.ep_off().astype(np.int64)
+    cnt = np.diff(off, append=need)                            # frames a call offers each endpoint
+    lens = rd.lens(0, need).astype(np.int64)
+    u = np.maximum(1, (lens + 15) // 16)
+    csum = np.concatenate([[0], np.cumsum(u)])
+    units = csum[np.minimum(off + cnt, need)] - csum[np.minimum(off, need)]   # ... and units
+    rd.free()
+    ids = int(np.flatnonzero(cnt)[-1]) + 1
+    pow2 = lambda v: np.where(v > 0, 2 ** np.ceil(np.log2(np.maximum(v, 1))), 0).astype(np.uint32)
+    D, B, total_u = pow2(cnt[:ids]), pow2(units[:ids]), int(units.sum())
+    with_slot = int(lens.max()) <= a.slot and int(lens.min()) > 0   # then both drains lay out the same bytes
+    sets = [lib.DeviceBRingSet(ctx, D, B) for _ in range(R)]
+    drs = [lib.DeviceDrain(ctx, need, 16 * total_u) for _ in range(R)]
+    ssets = [lib.DeviceRingSet(ctx, D, a.slot) for _ in range(R)] if with_slot else []
+    sdrs = [lib.DeviceDrain(ctx, need, need * a.slot) for _ in range(R)] if with_slot else []
+    for d in drs + sdrs:
+        d.set_budget([0xFFFFFFFF] * ids)
+    cp_src = ctx.alloc(16 * total_u)
+
+    def append(r):
+        ctx.deliver_brings(bs[r], rs[r], sets[r], s)
+
+    def bdrain(r):
+        ctx.drain_brings(sets[r], drs[r], s)
+
+    def sappend(r):
+        ctx.deliver_rings(bs[r], rs[r], ssets[r], s)
+
+    def sdrain(r):
+        ctx.drain_rings(ssets[r], sdrs[r], s)
+
+    def copy(r):
+        assert hip.hipMemcpyDtoDAsync(drs[r].desc.frames, cp_src.ptr, 16 * total_u, s) == 0
+
+    # the first append's rings against what the drain takes out of them: two endpoints
+    append(0)
+    hb = sets[0].info(s)
+    assert (hb.accepted, hb.accepted_units, hb.flags) == (need, total_u, 0), "the ample byte rings dropped"
+    queued = {e: sets[0].ring(e) for e in (2, ids - 1)}
+    bdrain(0)
+    h = drs[0].info(s, brings=True)
+    assert (h.selected, h.taken, h.need_bytes, h.flags) == (need, need, 16 * total_u, 0) and not sets[0].ring(2)[0].size
+    eo, boff = drs[0].ep_off(), drs[0].ep_boff()
+    for e, (qlens, qsrc, body) in queued.items():
+        k0, k1 = int(eo[e]), int(eo[e + 1])
+        assert np.array_equal(drs[0].lens(k0, k1), qlens) and np.array_equal(drs[0].src(k0, k1), qsrc)
+        assert np.array_equal(drs[0].bytes(int(boff[e]), int(boff[e + 1])), np.concatenate(body)), \
+            "ring %d drained differently" % e
+    paths = [("bdrain", bdrain, append), ("d2d_copy", copy, None)] + ([("slot_drain", sdrain, sappend)] if with_slot else [])
+    for r in list(range(1, R)) + list(range(R)) * 2:   # warm-up; every set ends drained
+        for _, fn, before in paths:
+            if before:
+                before(r)
+            fn(r)
+    us = {name: [] for name, _, _ in paths}
+    while len(us["bdrain"]) < a.launches:
+        for name, fn, before in paths:
+            us[name] += timed(fn, block, before=before)
+    for r in range(R):   # the last calls took everything
+        h = drs[r].info(s, brings=True)
+        assert (h.taken, h.need_bytes, h.flags) == (need, 16 * total_u, 0)
+        if with_slot:
+            hs = sdrs[r].info(s)
+            assert (hs.taken, hs.need_bytes, hs.flags) == (need, 16 * total_u, 0)
+    ref = "slot_drain" if with_slot else "d2d_copy"   # the comparison path's own spread in this run
+    blocks = [statistics.median(us[ref][i:i + block]) for i in range(0, len(us[ref]), block)]
+    out = dict(config=a.config, frames_per_call=n * Q, rings=Q, slot=a.slot, drained_frames=need,
+               need_bytes=16 * total_u, endpoints_with_a_ring=int((D > 0).sum()), descriptors=int(D.sum()),
+               units=int(B.sum()), unit_tile=lib.USN_BDRAIN_UTILE, launches=len(us["bdrain"]),
+               launches_per_call_bdrain=3, launches_per_call_slot_drain=4, spread_of=ref,
+               block_medians_us=[round(b, 1) for b in blocks])
+    for k, v in us.items():
+        out.update(stats(v, k))
+    out["bdrain_over_copy"] = round(out["bdrain_us"] / out["d2d_copy_us"], 2)
+    if with_slot:
+        out["slot_drain_over_copy"] = round(out["slot_drain_us"] / out["d2d_copy_us"], 2)
+        out["bdrain_over_slot_drain"] = round(out["bdrain_us"] / out["slot_drain_us"], 3)
     print(json.dumps(out), flush=True)
     if a.json:
         with open(a.json, "w") as fh:

@@ -4455,6 +4455,59 @@ int usn_rings_drain_info(usn_ctx *c, const usn_drain *d, void *stream, usn_drain
   return out->flags & (USN_DV_OVERFLOW_BYTES | USN_DR_BADCOUNT) ? USN_ERANGE : USN_OK;
 }
 
+/* ---- byte-ring drain: the consumer of a byte ring set (usn_brings_drain.hip) - */
+int usn_brings_drain(usn_ctx *c, usn_bringset *rs, usn_drain *d, void *stream) {
+  if (!c || !rs || !d) return USN_EINVAL;
+  if (!bringset_ok(rs) || !rs->ready || !drain_ok(d)) return USN_EINVAL;
+  if (c->reps.empty() || c->device < 0) return USN_ENODEV;
+  std::lock_guard<std::mutex> g(c->mu);
+  /* the replica usn_bringset_init laid the set out on: the selected one */
+  const Replica &R = c->reps[c->sel < c->reps.size() ? c->sel : 0];
+  HIPCHK(hipSetDevice(R.device));
+  usn::BDrainArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.frames = rs->frames;
+  a.lens = rs->lens;
+  a.src = rs->src;
+  a.pos16 = rs->pos16;
+  a.desc_off = rs->desc_off;
+  a.unit_off = rs->unit_off;
+  a.head = rs->head;
+  a.tail = rs->tail;
+  a.btail = rs->btail;
+  a.out_frames = d->frames;
+  a.out_off16 = d->off16;
+  a.out_lens = d->lens;
+  a.out_src = d->src;
+  a.ep_off = d->ep_off;
+  a.ep_boff = d->ep_boff;
+  a.budget = d->budget;
+  a.from = d->from;
+  a.take = d->take;
+  a.left = d->left;
+  a.hdr = d->hdr;
+  /* three per-id words inside drain_scratch_bytes: the ring drain's two, and the start of its tile area */
+  uint8_t *scratch = reinterpret_cast<uint8_t *>(d->hdr);
+  a.dtile_pfx = reinterpret_cast<uint32_t *>(scratch + usn::DELIVER_SCRATCH_OFF);
+  a.utile_pfx = a.dtile_pfx + USN_DT_IDS;
+  a.p0 = reinterpret_cast<uint32_t *>(scratch + usn::DRAIN_BASE_OFF);
+  a.total_desc = (uint32_t)rs->total_desc;
+  a.total_units = (uint32_t)rs->total_units;
+  a.cap = (uint32_t)d->cap;
+  a.cap_bytes = d->cap_bytes;
+  // the copy grid: what the device holds at once, as the other delivery grids
+  HIPCHK(usn::launch_brings_drain(a, (uint32_t)std::max(R.n_cu, 1) * 8u, (hipStream_t)stream));
+  return USN_OK;
+}
+
+int usn_brings_drain_info(usn_ctx *c, const usn_drain *d, void *stream, usn_drain_hdr *out) {
+  if (!c || !d || !d->hdr || !out) return USN_EINVAL;
+  if (c->reps.empty()) return USN_ENODEV;
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  HIPCHK(hipMemcpy(out, d->hdr, sizeof *out, hipMemcpyDeviceToHost));
+  return out->flags & (USN_DV_OVERFLOW_BYTES | USN_DR_BADCOUNT | USN_DR_BADDESC) ? USN_ERANGE : USN_OK;
+}
+
 /* ---- packed delivery: byte-compact rings (usn_deliver_packed.hip) ----------- */
 struct PDeliveryLayout {
   size_t frames, off16, lens, src, ep_off, ep_boff, hdr, total;

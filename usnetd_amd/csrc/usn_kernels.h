@@ -524,6 +524,54 @@ constexpr size_t brings_scratch_bytes(uint64_t total_desc) {
 }
 hipError_t launch_deliver_brings(const BRingsDeliverArgs &a, uint32_t grid, hipStream_t stream);
 
+/* ---- byte-ring drain (usn_brings_drain.hip): the consumer of a usn_bringset,
+ * into the ring drain's region (usn_drain).  The queued bytes of a byte ring
+ * are compact already, so nothing is summed or scanned per tile.  Three
+ * launches:
+ *   bdrain_plan_kernel    one workgroup: avail / want per id from desc_off,
+ *                         unit_off, head, tail, btail, budget and pos16 at the
+ *                         head descriptor, the ring drain's selection (from,
+ *                         take, left, ep_off), the units of every run from one
+ *                         more pos16 read (ep_boff, need_bytes, the overflow
+ *                         decision), the header, and two tile prefixes: over
+ *                         the selected descriptors and over the runs' units
+ *   bdrain_copy_kernel    device-sized grid: descriptor tiles (lens / src read
+ *                         from the ring, off16 from pos16, the chain check),
+ *                         then unit tiles (USN_BDRAIN_UTILE units of one run,
+ *                         copied unit for unit out of the wrapped byte ring)
+ *   bdrain_commit_kernel  one workgroup: unless bytes overflowed or a chain
+ *                         broke, head[] = from + take and taken = selected */
+struct BDrainArgs {
+  const uint8_t *frames;     /* the set's arrays: total_units units, total_desc descriptors, read only */
+  const uint16_t *lens;
+  const uint32_t *src;
+  const uint32_t *pos16;
+  const uint32_t *desc_off;  /* [USN_DT_IDS + 1] */
+  const uint32_t *unit_off;  /* [USN_DT_IDS + 1] */
+  uint32_t *head;            /* [USN_DT_IDS]: read by the plan, written by the commit */
+  const uint32_t *tail, *btail;   /* [USN_DT_IDS] */
+  uint8_t *out_frames;
+  uint32_t *out_off16;
+  uint16_t *out_lens;
+  uint32_t *out_src;
+  uint32_t *ep_off;          /* [USN_DT_IDS + 1] */
+  uint64_t *ep_boff;         /* [USN_DT_IDS + 1] */
+  const uint32_t *budget;    /* [USN_DT_IDS] */
+  uint32_t *from, *take, *left;   /* [USN_DT_IDS] each */
+  usn_drain_hdr *hdr;
+  /* scratch behind usn_drain.hdr, inside drain_scratch_bytes: the ring drain's tile_pfx and
+   * next_head places, and the first USN_DT_IDS words at DRAIN_BASE_OFF (12 * USN_DT_IDS bytes
+   * are there whatever cap is) */
+  uint32_t *dtile_pfx;       /* [USN_DT_IDS]: descriptor tiles of the selected runs of the ids below */
+  uint32_t *utile_pfx;       /* [USN_DT_IDS]: unit tiles of the runs of the ids below; all 0 on byte overflow */
+  uint32_t *p0;              /* [USN_DT_IDS]: pos16 at the head descriptor */
+  uint32_t total_desc, total_units;
+  uint32_t cap;
+  uint64_t cap_bytes;
+};
+static_assert(pdeliver_max_tiles(1) * 12 >= (size_t)USN_DT_IDS * 4, "p0 fits the drain's tile scratch");
+hipError_t launch_brings_drain(const BDrainArgs &a, uint32_t grid, hipStream_t stream);
+
 }  // namespace usn
 
 /* the same kernels at 512 threads per tile (a second compilation of

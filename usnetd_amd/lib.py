@@ -31,6 +31,8 @@ DV_DROPPED = 8          # usn_deliver_rings: an offered frame found its ring ful
 HAS_DELIVER_BRINGS = 1  # USN_HAS_DELIVER_BRINGS: the byte-compact persistent rings (usn_deliver_brings)
 DR_MORE = 16            # usn_rings_drain: a ring keeps queued frames after the call
 DR_BADCOUNT = 32        # usn_rings_drain: a ring's tail - head exceeds its size (not drained)
+DR_BADDESC = 64         # usn_brings_drain: a selected ring's pos16 / lens chain is inconsistent
+USN_BDRAIN_UTILE = 4096  # 16-byte units per copy tile of usn_brings_drain (usn_classify.h)
 R_WINDOW = 7
 PARITY_MASK = 0x00FFFFFF
 EP_NIC, EP_HOST, EP_PIPE, EP_UDS = 0, 1, 2, 3
@@ -239,6 +241,8 @@ def load(path: str | None = None):
         "usn_bringset_set_head": ([P, C.POINTER(BRingSet), P, U32, P], I),
         "usn_deliver_brings": ([P, P, P, U32, C.POINTER(BRingSet), P], I),
         "usn_deliver_brings_info": ([P, C.POINTER(BRingSet), P, C.POINTER(BRingSetHdr)], I),
+        "usn_brings_drain": ([P, C.POINTER(BRingSet), C.POINTER(Drain), P], I),
+        "usn_brings_drain_info": ([P, C.POINTER(Drain), P, C.POINTER(DrainHdr)], I),
     }
     optional = {"usn_set_frame_reader", "usn_ctx_create_group", "usn_ctx_replicas",
                 "usn_replica_select", "usn_replica_device", "usn_result_bytes_ep",
@@ -251,7 +255,7 @@ def load(path: str | None = None):
                 "usn_deliver_rings_info", "usn_drain_bytes", "usn_drain_bind", "usn_drain_set_budget",
                 "usn_rings_drain", "usn_rings_drain_info", "usn_bringset_bytes", "usn_bringset_bind",
                 "usn_bringset_init", "usn_bringset_set_head", "usn_deliver_brings",
-                "usn_deliver_brings_info"}   # A/B builds of older ABI versions lack these
+                "usn_deliver_brings_info", "usn_brings_drain", "usn_brings_drain_info"}   # A/B builds of older ABI versions lack these
     for name, (args, res) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -281,7 +285,7 @@ EXPORTED = ["usn_abi_version", "usn_strerror", "usn_last_hip_error", "usn_ctx_cr
             "usn_deliver_rings", "usn_deliver_rings_info", "usn_drain_bytes", "usn_drain_bind",
             "usn_drain_set_budget", "usn_rings_drain", "usn_rings_drain_info", "usn_bringset_bytes",
             "usn_bringset_bind", "usn_bringset_init", "usn_bringset_set_head", "usn_deliver_brings",
-            "usn_deliver_brings_info"]
+            "usn_deliver_brings_info", "usn_brings_drain", "usn_brings_drain_info"]
 
 
 def check(rc, what=""):
@@ -576,6 +580,12 @@ class Ctx:
         ra = (Result * n)(*[r.desc for r in results])
         check(self.L.usn_deliver_brings(self.h, C.cast(ba, C.c_void_p), C.cast(ra, C.c_void_p), n,
                                         C.byref(rs.desc), stream), "usn_deliver_brings")
+
+    def drain_brings(self, rs: "DeviceBRingSet", dr: "DeviceDrain", stream=None):
+        """Take up to dr's budgets of the oldest queued frames out of every byte ring
+        of `rs`, their units back to back in `dr`, and move the heads
+        (usn_brings_drain): three launches, no copy."""
+        check(self.L.usn_brings_drain(self.h, C.byref(rs.desc), C.byref(dr.desc), stream), "usn_brings_drain")
 
     def drain_rings(self, rs: "DeviceRingSet", dr: "DeviceDrain", stream=None):
         """Take up to dr's budgets of the oldest queued frames of every ring of
@@ -1077,7 +1087,8 @@ class DevicePackedDelivery:
 
 
 class DeviceDrain:
-    """One usn_drain: what a usn_rings_drain call takes out of a ring set --
+    """One usn_drain: what a usn_rings_drain call takes out of a ring set (or a
+    usn_brings_drain call out of a byte ring set) --
     cap_bytes of frames lying back to back (each padded to 16 bytes), off16[] /
     lens[] / src[] per output slot, the per-id slot and byte offsets, the
     budgets (input), from / take / left per id and the header.  `poison` as for
@@ -1105,13 +1116,15 @@ class DeviceDrain:
         check(self.ctx.L.usn_drain_set_budget(self.ctx.h, C.byref(self.desc), budget.ctypes.data,
                                               budget.size, stream), "usn_drain_set_budget")
 
-    def info(self, stream=None, strict=True) -> DrainHdr:
+    def info(self, stream=None, strict=True, brings=False) -> DrainHdr:
         """The header after the drain on `stream` finished.  strict: raise on
-        USN_DV_OVERFLOW_BYTES / USN_DR_BADCOUNT (USN_ERANGE); else return it with .status."""
+        USN_DV_OVERFLOW_BYTES / USN_DR_BADCOUNT (USN_ERANGE); else return it with .status.
+        brings: the call was usn_brings_drain (USN_DR_BADDESC is USN_ERANGE too)."""
         h = DrainHdr()
-        rc = self.ctx.L.usn_rings_drain_info(self.ctx.h, C.byref(self.desc), stream, C.byref(h))
+        name = "usn_brings_drain_info" if brings else "usn_rings_drain_info"
+        rc = getattr(self.ctx.L, name)(self.ctx.h, C.byref(self.desc), stream, C.byref(h))
         if strict or rc != USN_ERANGE:
-            check(rc, "usn_rings_drain_info")
+            check(rc, name)
         h.status = rc
         return h
 
